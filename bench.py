@@ -9,9 +9,17 @@ in HBM before the timed region (each receiver's ring holds a full slot, filled b
 synthetic source; the timed region re-commits it lap after lap without copying).
 
 Headline = the PRODUCT DEFAULT: the mode cwslg_create() hands out -- reference-order float32 arithmetic ("exact"), frames and candidate
-lists bit-identical to the reference chain's.  On one GPU the throughput mode (cwslg_set_exact(ctx, 0): fused polyphase form, audio within
-1e-5 of frame peak) is measured right after it on the same slots and reported as the "fast" record of the same JSON line.  --fast swaps
-the two; --primary-only skips the second record.
+lists bit-identical to the reference chain's.  --fast makes the throughput mode (cwslg_set_exact(ctx, 0): fused polyphase form, audio
+within 1e-5 of frame peak) the headline instead.
+
+A plain run sets up, warms up, times --steps steps, writes --dump-outputs and prints the line: nothing else.  --full adds what takes time
+of its own: on one GPU the other arithmetic mode measured right after the headline on the same slots (the second record of the same JSON
+line; --primary-only skips it), the oracle check of --verify slots after each timed region, and the CPU baseline (--no-cpu-baseline skips it).
+
+--dump-outputs DIR writes what the headline's last timed step computed, as a caller of the path receives it, for a fixed seeded sample of
+rank 0's slots (DUMP_SLOTS): DIR/audio_f32.npy (float frames), frame_i16.npy (int16 frames, as float32), frame_meta.npy (slot, t_start,
+n_valid, factor) and, with --sync, candidates.npy (one row per candidate: slot, freq_bin, time_step, sync, freq_hz, dt_s).  The inputs are a
+function of the arguments alone, so two builds can be compared output for output.
 
 Workload.  The north-star single-GPU workload -- 4096 FT8 slots resident on ONE MI355X (94 GB of IQ + 20 GB of frames,
 checkpoints and spectra) -- PER GPU at every N: the per-GPU work is fixed as N grows ("weak"; N = 8 carries 32 768 slots).
@@ -42,6 +50,7 @@ sys.path.insert(0, ROOT)
 FS = 192000
 IQ_LEN = 2048
 SLOT_SAMPLES = 2880000                    # 15 s FT8 slot at 192 kHz
+DUMP_SLOTS, DUMP_SEED = 16, 0             # --dump-outputs: 16 FT8 slots' frames (2 x 240 000 x 4 B each) = 31 MB of the 64 MB a dump may take
 HBM_PEAK_GBS = 8000.0                     # MI355X_MICROARCH.md: 8.0 TB/s spec
 BYTES_PER_SAMPLE_DEMOD = 8.0 + 4.0 / 16   # demod kernel: 8 B IQ read + 0.25 B float audio write
 BYTES_PER_SAMPLE_PATH = 8.625             # + finalise: 0.25 B read + 0.125 B int16 write
@@ -113,9 +122,12 @@ def parse_args(argv=None):
                          "(cwslg_rccl_init; no Python inside the boundary), torch = a torch.distributed all-reduce handed in as a callback; "
                          "auto = builtin on the nccl backend with one GPU per rank, torch otherwise (gloo, --same-device: RCCL refuses two ranks on one GPU)")
     ap.add_argument("--dry-run", action="store_true", help="launcher / process-group check without a GPU: every rank joins a gloo group, rank 0 prints the line's skeleton")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU-baseline wall time")
-    ap.add_argument("--verify", type=int, default=8, help="slots (spread over the whole range) checked against the oracle after the timed region")
+    ap.add_argument("--full", action="store_true", help="also measure the second arithmetic mode, check --verify slots against the oracle and run the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the headline's last-step outputs for a fixed sample of slots as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="(--full) target CPU-baseline wall time")
+    ap.add_argument("--verify", type=int, default=None,
+                    help="(--full) slots (spread over the whole range) checked against the oracle after the timed region; default 8")
     ap.add_argument("--no-spans", action="store_true", help="diagnostic: no HIP timing events around the kernels (roofline fields are then empty)")
     ap.add_argument("--host-timing", action="store_true", help="print the host time spent inside each asynchronous call of a step (stderr)")
     args = ap.parse_args(argv)
@@ -123,6 +135,10 @@ def parse_args(argv=None):
         args.fast, args.primary_only = True, True
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.verify is None:
+        args.verify = 8 if args.full else 0
+    elif args.verify > 0 and not args.full:
+        ap.error("--verify checks against the oracle, which only a --full run does")
     return args
 
 
@@ -514,19 +530,44 @@ def main():
         return {"mode": MODE_TEXT[exact], "value": float(world) * spl * args.steps / dt_ / 1e6, "unit": "Msamples/s", "steps": args.steps,
                 "warmup": args.warmup, "ms_per_step": dt_ / args.steps * 1e3, "roofline": roof, "roofline_sync": roofline_sync(st_), "verify": ver}
 
-    # The headline record is the product default (exact) unless --fast; on one GPU the other mode is measured right after it on the same slots.
+    def dump_outputs(path):
+        """The frames (and candidate lists) the last timed step left in a fixed seeded sample of rank 0's slots, as float32 / float64 .npy."""
+        if rank != 0:
+            return
+        os.makedirs(path, exist_ok=True)
+        picks = np.sort(np.random.default_rng(DUMP_SEED).choice(S, size=min(DUMP_SLOTS, S), replace=False))
+        audio, i16, meta, cands = [], [], [], []
+        for s in picks:
+            a, _ = ctx.fetch_audio_f32(chans[s])
+            g = ctx.fetch_frame(chans[s])
+            audio.append(a)
+            i16.append(g["i16"].astype(np.float32))
+            meta.append((s, g["t_start"], g["n_valid"], float(g["factor"])))
+            if args.sync:
+                cands += [(s,) + tuple(c) for c in ctx.fetch_candidates(chans[s])]
+        out = {"audio_f32": np.stack(audio), "frame_i16": np.stack(i16), "frame_meta": np.array(meta, np.float64)}
+        if args.sync:
+            out["candidates"] = np.array(cands, np.float64).reshape(-1, 6)
+        assert sum(v.nbytes for v in out.values()) <= 64 << 20
+        for name, v in out.items():
+            np.save(os.path.join(path, name + ".npy"), v)
+
+    # The headline record is the product default (exact) unless --fast; with --full, on one GPU the other mode is measured right after it
+    # on the same slots.
     primary_exact = not args.fast
     dt, st, kernel_name = timed_region(primary_exact)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs)
     verify = verify_against_oracle(primary_exact)
     second = None
-    if not args.primary_only and world == 1:
+    if args.full and not args.primary_only and world == 1:
         dt2, st2, kname2 = timed_region(not primary_exact)
         ver2 = verify_against_oracle(not primary_exact)
         second = (not primary_exact, dt2, st2, kname2, ver2)
 
     # ---- CPU baseline: the reference's own code in the reference's shape, on this box's host cores (rank 0, N=1 only)
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import oracle as O
         cores = host_cores()
         n_eff = SLOT_SAMPLES // IQ_LEN * IQ_LEN       # the CPU drivers push whole blocks only

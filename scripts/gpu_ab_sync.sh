@@ -3,7 +3,7 @@
 O=$GRAFT_REPO_ROOT/gpurun_out/ab; mkdir -p $O; cd $GRAFT_REPO_ROOT
 for S in ${SLOTS_LIST:-512 4096}; do
 for V in ${VARIANTS:-0 1 2 3}; do
-  CWSLG_SYNC_VARIANT=$V timeout 600 python bench.py --slots $S --steps 10 --warmup 3 --no-cpu-baseline --verify 0 > $O/ab_${S}_v$V.json 2> $O/ab_${S}_v$V.err
+  CWSLG_SYNC_VARIANT=$V timeout 600 python bench.py --full --slots $S --steps 10 --warmup 3 --no-cpu-baseline --verify 0 > $O/ab_${S}_v$V.json 2> $O/ab_${S}_v$V.err
   python3 - <<PY
 import json
 d=json.load(open("$O/ab_${S}_v$V.json")); r=d["roofline"]

@@ -2,10 +2,10 @@
 # CWSLG_DEMOD_VARIANT=8 (split-bf16 matrix-core FIR): parity in the default mode, time, package power
 cd $GRAFT_REPO_ROOT
 CWSLG_DEMOD_VARIANT=8 timeout 900 python -m pytest tests/test_gpu_demod.py tests/test_gpu_golden.py tests/test_gpu_properties.py -x -q -m gpu 2>&1 | grep -v "^$" | tail -6
-CWSLG_DEMOD_VARIANT=8 timeout 300 python bench.py --slots 64 --sync 0 --steps 5 --warmup 2 --no-cpu-baseline --verify 8 2>&1 | tail -1 | python3 -c "
+CWSLG_DEMOD_VARIANT=8 timeout 300 python bench.py --full --slots 64 --sync 0 --steps 5 --warmup 2 --no-cpu-baseline --verify 8 2>&1 | tail -1 | python3 -c "
 import sys,json; d=json.loads(sys.stdin.read()); print('variant 8 verify', d['verify'])"
 sample() {
-  (env CWSLG_DEMOD_VARIANT=$1 timeout 100 python bench.py --slots 512 --sync 0 --steps 5000 --warmup 2 --no-cpu-baseline --verify 0 > /tmp/pv.json 2>/dev/null) &
+  (env CWSLG_DEMOD_VARIANT=$1 timeout 100 python bench.py --full --slots 512 --sync 0 --steps 5000 --warmup 2 --no-cpu-baseline --verify 0 > /tmp/pv.json 2>/dev/null) &
   BP=$!
   sleep 9
   P=""; C=""

@@ -3,7 +3,7 @@
 # without the split arithmetic (diag2), against the traffic-only probe (variant 9).  512 slots, demod only; time, power, clock.
 cd $GRAFT_REPO_ROOT
 sample() { # label variant lib
-  (env CWSLG_DEMOD_VARIANT=$2 CWSLG_LIB=$3 timeout 100 python bench.py --slots 512 --sync 0 --steps 5000 --warmup 2 --no-cpu-baseline --verify 0 > /tmp/pv.json 2>/dev/null) &
+  (env CWSLG_DEMOD_VARIANT=$2 CWSLG_LIB=$3 timeout 100 python bench.py --full --slots 512 --sync 0 --steps 5000 --warmup 2 --no-cpu-baseline --verify 0 > /tmp/pv.json 2>/dev/null) &
   BP=$!
   sleep 9
   P=""; C=""

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Idle gaps between the kernels of a bench step (rocprofv3 kernel trace timestamps): where step time minus kernel time goes
 O=$GRAFT_REPO_ROOT/gpurun_out/gaps; mkdir -p $O; export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; cd /tmp
-timeout 600 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $O/t -- python3 $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline --verify 0 ${BENCH_ARGS:-} > $O/run.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $O/t -- python3 $R/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --verify 0 ${BENCH_ARGS:-} > $O/run.log 2>&1
 cd $R
 python3 - <<'PY'
 import csv, glob, os

@@ -3,7 +3,7 @@
 #   9 = traffic-only probe (same loads and stores, no arithmetic), 0 = demod_kernel, 7 = FIR on the matrix cores, exact = exact mode
 cd $GRAFT_REPO_ROOT
 sample() { # label, env, args
-  (env $2 timeout 100 python bench.py --slots 512 --sync 0 --steps 6000 --warmup 2 --no-cpu-baseline --verify 0 $3 > /tmp/pv.json 2>/dev/null) &
+  (env $2 timeout 100 python bench.py --full --slots 512 --sync 0 --steps 6000 --warmup 2 --no-cpu-baseline --verify 0 $3 > /tmp/pv.json 2>/dev/null) &
   BP=$!
   sleep 9
   P=""; C=""

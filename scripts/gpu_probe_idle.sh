@@ -1,4 +1,4 @@
-run() { python bench.py --steps 8 --warmup 2 --no-cpu-baseline --sync 0 --verify 0 2>/dev/null | python -c "
+run() { python bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --sync 0 --verify 0 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 print('$1 %.3f ms' % (r['avg_launch_ms']))"; }

@@ -7,7 +7,7 @@ timeout 1500 python -m pytest tests/test_gpu_exact.py tests/test_gpu_demod.py te
 for cfg in "asm|CWSLG_LIB=|512" "c++|CWSLG_LIB=lab CWSLG_DEMOD_VARIANT=25|512" "asm|CWSLG_LIB=|4096" "c++|CWSLG_LIB=lab CWSLG_DEMOD_VARIANT=25|4096" "asm|CWSLG_LIB=|4096"; do
   IFS='|' read label envs slots <<< "$cfg"
   f=$O/r3_exactasm_${label}_${slots}.json
-  env $envs timeout 300 python3 bench.py --slots $slots --exact --sync 0 --steps 10 --warmup 3 --no-cpu-baseline --verify 8 > $f 2> $f.err || tail -5 $f.err
+  env $envs timeout 300 python3 bench.py --full --slots $slots --exact --sync 0 --steps 10 --warmup 3 --no-cpu-baseline --verify 8 > $f 2> $f.err || tail -5 $f.err
   python3 - <<PY
 import json
 d=json.loads(open("$f").read().strip().splitlines()[-1])

@@ -7,7 +7,7 @@ tail -4 $O/r4_exact4_tests.log
 for cfg in "x4|CWSLG_LIB=|512" "x3|CWSLG_LIB=lab CWSLG_DEMOD_VARIANT=26|512" "x4|CWSLG_LIB=|4096" "x3|CWSLG_LIB=lab CWSLG_DEMOD_VARIANT=26|4096" "x4|CWSLG_LIB=|4096"; do
   IFS='|' read label envs slots <<< "$cfg"
   f=$O/r4_exact4_${label}_${slots}.json
-  env $envs timeout 300 python3 bench.py --slots $slots --primary-only --sync 0 --steps 10 --warmup 3 --no-cpu-baseline --verify 8 > $f 2> $f.err || tail -5 $f.err
+  env $envs timeout 300 python3 bench.py --full --slots $slots --primary-only --sync 0 --steps 10 --warmup 3 --no-cpu-baseline --verify 8 > $f 2> $f.err || tail -5 $f.err
   python3 - <<PY
 import json
 d=json.loads(open("$f").read().strip().splitlines()[-1])

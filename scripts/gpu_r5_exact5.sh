@@ -9,7 +9,7 @@ fi
 for cfg in "x5|CWSLG_LIB=|512" "x4|CWSLG_LIB=lab CWSLG_DEMOD_VARIANT=27|512" "x5|CWSLG_LIB=|4096" "x4|CWSLG_LIB=lab CWSLG_DEMOD_VARIANT=27|4096" "x5s704|CWSLG_LIB=lab CWSLG_EXACT5_SEG=704|4096" "x5s2816|CWSLG_LIB=lab CWSLG_EXACT5_SEG=2816|4096" "x5s352|CWSLG_LIB=lab CWSLG_EXACT5_SEG=352|4096"; do
   IFS='|' read label envs slots <<< "$cfg"
   f=$O/r5_exact5_${label}_${slots}.json
-  env $envs timeout 300 python3 bench.py --slots $slots --primary-only --sync 0 --steps 10 --warmup 3 --no-cpu-baseline --verify 8 > $f 2> $f.err || tail -5 $f.err
+  env $envs timeout 300 python3 bench.py --full --slots $slots --primary-only --sync 0 --steps 10 --warmup 3 --no-cpu-baseline --verify 8 > $f 2> $f.err || tail -5 $f.err
   python3 - <<PY
 import json
 try:

@@ -12,7 +12,7 @@ from cwsl_digi_amd import build as B
 B.build(force=True)" > /dev/null 2>&1 || { echo "$label: build failed"; continue; }
   for rep in 1 2; do
   f=$O/r5_x5var_${label}.json
-  timeout 300 python3 bench.py --slots 4096 --primary-only --sync 0 --steps 10 --warmup 3 --no-cpu-baseline --verify 4 > $f 2> $f.err || tail -5 $f.err
+  timeout 300 python3 bench.py --full --slots 4096 --primary-only --sync 0 --steps 10 --warmup 3 --no-cpu-baseline --verify 4 > $f 2> $f.err || tail -5 $f.err
   python3 - <<PY
 import json
 try:

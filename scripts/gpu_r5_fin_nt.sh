@@ -7,7 +7,7 @@ for v in 0 1 3 2 0 1 3 2; do
 from cwsl_digi_amd import build as B
 B.build(force=True)" > /dev/null 2>&1 || { echo "fin_nt=$v: build failed"; continue; }
   f=$O/r5_fin_nt_$v.json
-  timeout 300 python3 bench.py --slots 4096 --fast --primary-only --steps 10 --warmup 3 --no-cpu-baseline --verify 2 > $f 2> $f.err || tail -3 $f.err
+  timeout 300 python3 bench.py --full --slots 4096 --fast --primary-only --steps 10 --warmup 3 --no-cpu-baseline --verify 2 > $f 2> $f.err || tail -3 $f.err
   python3 - <<PY
 import json
 d=json.loads(open("$f").read().strip().splitlines()[-1]); r=d["roofline"]; s=d["roofline_sync"]

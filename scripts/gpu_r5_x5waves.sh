@@ -7,7 +7,7 @@ for v in ${VARIANTS:-4 2 1 8 4 2 1 8}; do
 from cwsl_digi_amd import build as B
 B.build(force=True)" > /dev/null 2>&1 || { echo "waves=$v: build failed"; continue; }
   f=$O/r5_x5waves_$v.json
-  timeout 300 python3 bench.py --slots 4096 --primary-only --sync 0 --steps 10 --warmup 3 --no-cpu-baseline --verify 4 > $f 2> $f.err || tail -3 $f.err
+  timeout 300 python3 bench.py --full --slots 4096 --primary-only --sync 0 --steps 10 --warmup 3 --no-cpu-baseline --verify 4 > $f 2> $f.err || tail -3 $f.err
   python3 - <<PY
 import json
 d=json.loads(open("$f").read().strip().splitlines()[-1]); r=d["roofline"]

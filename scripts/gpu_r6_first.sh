@@ -25,4 +25,4 @@ for k, v in out.items():
     else: print(k, v)
 PY
 timeout 900 python3 scripts/gpu_rates_exact.py --slots 4096 > $O/rates4096.json 2> $O/rates4096.err; cat $O/rates4096.err | tail -8
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err; tail -c 1500 $O/bench_default.json
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; tail -c 1500 $O/bench_default.json

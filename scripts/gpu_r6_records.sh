@@ -33,7 +33,7 @@ for k, v in out.items():
 PY
 timeout 900 python3 scripts/run_configs.py --config 3 > $O/config3_1024mixed.json 2> $O/config3.err || tail -3 $O/config3.err
 timeout 1200 python3 scripts/run_configs.py --config 5 > $O/config5_256long.json 2> $O/config5.err || tail -3 $O/config5.err
-timeout 600 python3 bench.py --channels-per-rx 128 --no-cpu-baseline > $O/bench_shared_32x128.json 2> $O/shared.err || tail -3 $O/shared.err
+timeout 600 python3 bench.py --full --channels-per-rx 128 --no-cpu-baseline > $O/bench_shared_32x128.json 2> $O/shared.err || tail -3 $O/shared.err
 timeout 900 python3 scripts/e2e_report.py > $O/e2e_candidates.json 2> $O/e2e.err || tail -3 $O/e2e.err
 timeout 900 python3 scripts/gpu_rates_exact.py --slots 4096 > $O/rates4096.json 2> $O/rates4096.err; tail -6 $O/rates4096.err
 tail -c 600 $O/config3_1024mixed.json; echo; tail -c 600 $O/config5_256long.json; echo; tail -c 400 $O/bench_shared_32x128.json; echo; tail -c 600 $O/e2e_candidates.json

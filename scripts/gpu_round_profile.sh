@@ -3,11 +3,11 @@
 # (3) PMC passes (separate runs) for HBM traffic + SQ counters.  Everything lands in gpurun_out/round/.
 O=$GRAFT_REPO_ROOT/gpurun_out/round; mkdir -p $O; export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT
 cd $R
-timeout 900 python bench.py > $O/bench_default.json 2> $O/bench_default.err
+timeout 900 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 cd /tmp
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --no-cpu-baseline --verify 0 > $O/stats.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --full --no-cpu-baseline --verify 0 > $O/stats.log 2>&1
 run() { name=$1; shift
-  timeout 600 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $O/pmc_$name -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --verify 0 > $O/pmc_$name.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --pmc "$@" --output-format csv -d $O/pmc_$name -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --verify 0 > $O/pmc_$name.log 2>&1
 }
 run fetch FETCH_SIZE GRBM_GUI_ACTIVE
 run write WRITE_SIZE GRBM_COUNT

@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
 """Generate tests/golden/*.npz from the REFERENCE ITSELF (oracle/_ref = unmodified SSBD.hpp/LowPass.hpp
-compiled in place with g++ -std=c++17 -O2 -ffp-contract=off).  Run in the build container only:
+compiled in place with g++ -std=c++17 -O2 -ffp-contract=off).  Run where the reference headers are at hand:
 
-    make -C oracle ref && python tests/gen_golden.py
+    make -C oracle ref && python tests/gen_golden.py          # every fixture
+    make -C oracle ref && python tests/gen_golden.py ref      # only tests/golden/ref_*.npz (tests/test_oracle_vs_ref.py)
 
 The fixtures hold inputs as seeds (the portable generator of oracle/cwsl_oracle.c regenerates them) and
 expected outputs as raw bit patterns / samples / checksums -- data only, no reference source.
 Rows a8/a9 (prepareAudio, int16) have no compilable reference (Instance.cpp needs Win32); their
 expectations are this repo's restatement applied to the reference's SSBD output.
 """
+import hashlib
 import os
 import sys
 
@@ -101,6 +103,72 @@ def gen_adversarial():
               % (float(peak), int(np.abs(audio).argmax()), float(np.abs(iq).max()), float(factor), O.crc32(i16)))
 
 
+def _ref_error(fn, *args):
+    try:
+        fn(*args)
+    except ValueError as e:
+        return str(e)
+    raise SystemExit(f"the reference accepted {args}")
+
+
+def gen_ref():
+    """tests/ref_cases.py's inputs through the reference's own SSBD, Instance framing and helpers (oracle/_ref): what
+    tests/test_oracle_vs_ref.py compares the restatement with."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import ref_cases as RC
+    for fs, f, usb in RC.DEMOD_CASES:
+        audio, trace = O.RefDemod(fs, float(f), usb=usb).run(RC.demod_iq(O, fs, f, usb), trace=True)
+        np.savez_compressed(os.path.join(OUT, RC.demod_file(fs, f, usb)), audio_bits=audio.view(np.uint32), trace_bits=trace.view(np.uint64))
+    for mode, fs, blk, f in RC.FRAMING_CASES:
+        ri = O.RefInstance(mode, fs, blk, f)
+        took, emitted, t0, nw, frames = [], [], [], [], []
+        for blocks, epoch in RC.framing_schedule(O, mode, fs, blk, f):
+            took += [ri.push(b) for b in blocks]
+            e, t, n, fr = ri.boundary(epoch)
+            emitted.append(e); t0.append(t); nw.append(n)
+            if e:
+                frames.append(fr.view(np.uint32))
+        # the emitted float frames in full would pass the size limit of a fixture: their bits as SHA-256 digests, plus each frame's head
+        np.savez_compressed(os.path.join(OUT, RC.framing_file(mode, fs, blk, f)), took=np.array(took, np.int8), emitted=np.array(emitted),
+                            t_start=np.array(t0, np.uint64), n_written=np.array(nw, np.uint64),
+                            frame_sha256=np.array([hashlib.sha256(fr.tobytes()).hexdigest() for fr in frames]),
+                            frame_head_bits=np.stack([fr[:1024] for fr in frames]))
+    R = O.ref()
+    r = O.RefDemod(192000, 0.0)
+    getters = [R.ref_ssbd_in_size(r.h), R.ref_ssbd_out_size(r.h), R.ref_ssbd_out_rate(r.h), R.ref_ssbd_delay(r.h), r.ntaps, r.block]
+    lowpass = []
+    for order, bw in RC.LOWPASS_CASES:
+        t = np.empty(order, np.float32)
+        R.ref_build_lowpass(order, bw, t)
+        lowpass.append(t.view(np.uint32))
+    locs, padded = RC.helper_strings()
+    fs, iq, n1, f0, bad, f1 = RC.tune_live_case(O)
+    b = O.RefDemod(fs, f0)
+    live = [b.run(iq[:n1])]
+    live_err = _ref_error(b.tune, bad)
+    b.tune(f1)
+    live.append(b.run(iq[n1:]))
+    live_tone = b.tone
+    fs, iq, f0, cuts, plan = RC.tune_noreset_case(O)
+    b = O.RefDemod(fs, f0)
+    noreset = []
+    for k in range(3):
+        if plan[k] is not None:
+            b.tune(plan[k][0], plan[k][1], reset=False)
+        noreset.append(b.run(iq[cuts[k]:cuts[k + 1]]).view(np.uint32))
+    np.savez_compressed(
+        os.path.join(OUT, "ref_misc.npz"), getters_192k=np.array(getters, np.uint64),
+        bad_demod_errors=np.array([_ref_error(O.RefDemod, *a) for a in RC.BAD_DEMODS]),
+        **{f"lowpass_{k}_bits": t for k, t in enumerate(lowpass)},
+        mode_groups=np.array([O.ref_mode_group(m) for m in RC.MODES], np.int32),
+        locators=np.array(locs), locator_valid=np.array([O.ref_is_valid_locator(x) for x in locs]),
+        trimmed=np.array([O.ref_trim(x) for x in padded]),
+        tune_live_bits_0=live[0].view(np.uint32), tune_live_bits_1=live[1].view(np.uint32), tune_live_error=np.array(live_err),
+        tune_live_tone_bits=live_tone.view(np.uint32),
+        **{f"tune_noreset_bits_{k}": y for k, y in enumerate(noreset)})
+    print("ref fixtures:", len(RC.DEMOD_CASES), "demod,", len(RC.FRAMING_CASES), "framing, misc")
+
+
 def main():
     if not O.have_ref():
         raise SystemExit("oracle/_ref/libcwsl_ref.so missing: run `make -C oracle ref` where /root/reference exists")
@@ -117,7 +185,13 @@ def main():
     gen_slot("wspr_fs192000_f1500", "WSPR", 192000, 1500, 0x3535, 23040000 // 2048 * 2048, 2048)
     gen_slot("fst4w120_fs192000_f1500", "FST4W-120", 192000, 1500, 0x3535, 23040000 // 2048 * 2048, 2048)
     gen_adversarial()
+    gen_ref()
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["ref"]:
+        if not O.have_ref():
+            raise SystemExit("oracle/_ref/libcwsl_ref.so missing: run `make -C oracle ref` where the reference headers are")
+        gen_ref()
+    else:
+        main()

@@ -169,7 +169,7 @@ def test_bench_py_gpus_2_launches_two_ranks_on_this_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--same-device", "--dist-backend", "gloo", "--slots", "64",
-                        "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--verify", "2"], capture_output=True, text=True, timeout=900, env=env, cwd=root)
+                        "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--verify", "2"], capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["steps"] == 3
@@ -188,7 +188,7 @@ def test_bench_py_falls_back_loudly_when_the_builtin_communicator_cannot_come_up
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--same-device", "--dist-backend", "gloo", "--rendezvous", "builtin",
-                        "--slots", "64", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--verify", "1", "--primary-only"],
+                        "--slots", "64", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--verify", "1", "--primary-only"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert p.returncode == 0, p.stderr[-3000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])

@@ -1,156 +1,137 @@
-"""CPU: oracle restatement vs the compiled reference headers (oracle/_ref), where that build exists
-(the build container; on the GPU box the prebuilt .so travels with the snapshot)."""
+"""CPU: oracle restatement vs the compiled reference headers (oracle/_ref), through what they returned for the inputs of
+tests/ref_cases.py: tests/golden/ref_*.npz, recorded by `python tests/gen_golden.py ref` where the reference can be built."""
+import hashlib
+import os
+
 import numpy as np
 import pytest
 
+import ref_cases as RC
+
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def _gold(name):
+    with np.load(os.path.join(GOLD, name)) as z:
+        return {k: z[k] for k in z.files}
+
 
 @pytest.fixture(scope="module")
-def ref(oracle):
-    if not oracle.have_ref():
-        pytest.skip("oracle/_ref/libcwsl_ref.so not built (needs /root/reference)")
-    return oracle
+def misc():
+    return _gold("ref_misc.npz")
 
 
-@pytest.mark.parametrize("fs,f,usb", [(192000, -26000, True), (192000, 90000, True), (192000, 12000, False),
-                                      (96000, -30000, True), (48000, 9000, True), (48000, -3000, False)])
-def test_bit_identical_audio_and_phasor(ref, fs, f, usb):
-    D = fs // 12000
-    n = 4 * D * 3000
-    iq = ref.synth_iq(fs ^ (f & 0xFFFF), n, fs, tones_hz=[f + 1000.0, f - 1800.0 if not usb else f + 2222.0], amp=1e4)
-    a, ta = ref.Demod(fs, float(f), usb=usb).run(iq, trace=True)
-    b, tb = ref.RefDemod(fs, float(f), usb=usb).run(iq, trace=True)
-    assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
-    assert np.array_equal(ta.view(np.uint64), tb.view(np.uint64))
+@pytest.mark.parametrize("fs,f,usb", RC.DEMOD_CASES)
+def test_bit_identical_audio_and_phasor(oracle, fs, f, usb):
+    g = _gold(RC.demod_file(fs, f, usb))
+    a, ta = oracle.Demod(fs, float(f), usb=usb).run(RC.demod_iq(oracle, fs, f, usb), trace=True)
+    assert np.array_equal(a.view(np.uint32), g["audio_bits"])
+    assert np.array_equal(ta.view(np.uint64), g["trace_bits"])
 
 
-def test_getters_and_errors(ref):
-    r = ref.RefDemod(192000, 0.0)
-    R = ref.ref()
-    assert (R.ref_ssbd_in_size(r.h), R.ref_ssbd_out_size(r.h), R.ref_ssbd_out_rate(r.h), R.ref_ssbd_delay(r.h)) == (64, 4, 12000, 8)
-    for args, msg in (((192000, 97000.0), "low"), ((192000, 93000.0), "high")):
-        with pytest.raises(ValueError) as e1:
-            ref.RefDemod(*args)
+def test_getters_and_errors(oracle, misc):
+    in_size, out_size, out_rate, delay, ntaps, block = (int(x) for x in misc["getters_192k"])
+    assert (in_size, out_size, out_rate, delay) == (64, 4, 12000, 8)
+    d = oracle.Demod(192000, 0.0)
+    assert (d.ntaps, d.block, 4 * d.block) == (ntaps, block, in_size)
+    for args, want, msg in zip(RC.BAD_DEMODS, misc["bad_demod_errors"], ("low", "high", None)):
         with pytest.raises(ValueError) as e2:
-            ref.Demod(*args)
-        assert msg in str(e1.value) and str(e1.value) == str(e2.value)
-    with pytest.raises(ValueError) as e1:
-        ref.RefDemod(44100, 0.0)
-    with pytest.raises(ValueError) as e2:
-        ref.Demod(44100, 0.0)
-    assert str(e1.value) == str(e2.value) == "Fs/B must be an even integer >= 4"
+            oracle.Demod(*args)
+        assert str(e2.value) == str(want)
+        if msg:
+            assert msg in str(want)
+    assert str(misc["bad_demod_errors"][2]) == "Fs/B must be an even integer >= 4"
 
 
-def test_lowpass_design_matches(ref):
-    for order, bw in ((512, 6000 / 192000.), (256, 6000 / 96000.), (128, 0.125)):
-        a = np.empty(order, np.float32); b = np.empty(order, np.float32)
-        ref.lib().orc_lowpass_design(order, bw, a)
-        ref.ref().ref_build_lowpass(order, bw, b)
-        assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
+def test_lowpass_design_matches(oracle, misc):
+    for k, (order, bw) in enumerate(RC.LOWPASS_CASES):
+        a = np.empty(order, np.float32)
+        oracle.lib().orc_lowpass_design(order, bw, a)
+        assert np.array_equal(a.view(np.uint32), misc[f"lowpass_{k}_bits"])
 
 
 # ---- slot framing: the oracle's Channel against Instance's sequences replayed on the reference's own containers ----
-@pytest.mark.parametrize("mode,fs,blk,f", [("FT4", 48000, 1024, 3000), ("FT8", 96000, 2048, -20000), ("FT4", 192000, 2048, 50000)])
-def test_framing_matches_reference_containers(ref, mode, fs, blk, f):
+@pytest.mark.parametrize("mode,fs,blk,f", RC.FRAMING_CASES)
+def test_framing_matches_reference_containers(oracle, mode, fs, blk, f):
     """Random schedules of blocks and boundaries, including over-full slots ("af buffer full"), empty slots and the
     discarded first frame: same drop decisions, same epochs, same sample counts, bit-identical float frames."""
-    rng = np.random.default_rng(fs + blk)
-    oc = ref.Channel(mode, fs, blk, f)
-    ri = ref.RefInstance(mode, fs, blk, f)
-    dec = fs // 12000
-    cap_blocks = (oc.frame_len - 1) // (blk // dec)              # blocks a frame accepts before the guard trips
-    epoch = 1000
-    n_emit = n_drop = 0
-    for slot in range(6):
-        n_blocks = [cap_blocks // 3, 0, cap_blocks + 5, 1, cap_blocks, 7][slot]
-        iq = ref.synth_iq(100 + slot, max(1, n_blocks) * blk, fs, tones_hz=[f + 1500.0], amp=8000.0)
-        for k in range(n_blocks):
-            b = iq[k * blk:(k + 1) * blk]
-            took_o, took_r = oc.push(b), ri.push(b)
-            assert took_o == took_r
-            n_drop += 1 - took_r
-        epoch += int(rng.integers(1, 20))
+    g = _gold(RC.framing_file(mode, fs, blk, f))
+    oc = oracle.Channel(mode, fs, blk, f)
+    assert oc.frame_len == oracle.frame_len(mode)
+    took, n_emit = [], 0
+    for slot, (blocks, epoch) in enumerate(RC.framing_schedule(oracle, mode, fs, blk, f)):
+        took += [oc.push(b) for b in blocks]
         fo = oc.boundary(epoch, want_f32=True)
-        emitted, t0, nw, fr = ri.boundary(epoch)
-        assert (fo is not None) == emitted
-        if emitted:
+        assert (fo is not None) == bool(g["emitted"][slot])
+        if fo is not None:
+            assert fo["t_start"] == int(g["t_start"][slot])
+            assert np.array_equal(fo["f32"][:1024].view(np.uint32), g["frame_head_bits"][n_emit])
+            assert hashlib.sha256(fo["f32"].view(np.uint32).tobytes()).hexdigest() == str(g["frame_sha256"][n_emit])
             n_emit += 1
-            assert fo["t_start"] == t0
-            assert np.array_equal(fo["f32"].view(np.uint32), fr.view(np.uint32))
+    assert took == [int(t) for t in g["took"]]
+    n_drop = len(took) - sum(took)
     assert n_emit == 5 and n_drop >= 5                           # first frame discarded; the over-full slot dropped blocks
 
 
-def test_mode_groups_match_syncpredicates(ref):
+def test_mode_groups_match_syncpredicates(misc):
     import cwsl_digi_amd as P
-    modes = ["FT8", "JS8", "FT4", "WSPR", "Q65-30", "JT65", "FST4-60", "FST4-120", "FST4-300", "FST4-900", "FST4-1800",
-             "FST4W-120", "FST4W-300", "FST4W-900", "FST4W-1800"]
-    for m in modes:
-        g = ref.ref_mode_group(m)
+    for m, g in zip(RC.MODES, misc["mode_groups"]):
+        if m == "PSK31":
+            assert g == -1
+            continue
         assert g == P.group_of(m) == P.parse_decoder_line(f"14074000 {m}", 1.0)["group"], m
-    assert ref.ref_mode_group("PSK31") == -1
     with pytest.raises(Exception):
         P.parse_decoder_line("14074000 PSK31", 1.0)
 
 
-def test_locator_and_trim_helpers_match_reference(ref):
-    import random
+def test_locator_and_trim_helpers_match_reference(oracle, misc):
     import cwsl_digi_amd as P
-    rng = random.Random(5)
-    alphabet = "ABfn0199 -/x"
-    for _ in range(400):
-        loc = "".join(rng.choice(alphabet) for _ in range(rng.choice([3, 4, 4, 4, 5])))
-        if " " in loc:
-            continue
+    locs, padded = RC.helper_strings()
+    assert locs == [str(x) for x in misc["locators"]]
+    for loc, valid in zip(locs, misc["locator_valid"]):
         line = f"123045 -12  0.3 1234 ~  CQ K1ABC {loc}"
         got = P.parse_decode_line("FT8", line, 0)
-        want = ref.parse_decode_line("FT8", line, 0)
+        want = oracle.parse_decode_line("FT8", line, 0)
         assert got == want
         if got["status"] == "ok" and got["call"] == "K1ABC":
-            assert (got["locator"] is not None) == ref.ref_is_valid_locator(loc), loc
-    for _ in range(200):
-        pad_l = "".join(rng.choice(" \t") for _ in range(rng.randrange(0, 4)))
-        pad_r = "".join(rng.choice(" \t\r\n") for _ in range(rng.randrange(0, 4)))
-        core = "123045 -12  0.3 1234 ~  CQ K1ABC FN42"
-        assert ref.ref_trim(pad_l + core + pad_r) == core
-        assert P.parse_decode_line("FT8", pad_l + core + pad_r, 0)["call"] == "K1ABC"
+            assert (got["locator"] is not None) == bool(valid), loc
+    for line, trimmed in zip(padded, misc["trimmed"]):
+        assert str(trimmed) == RC.TRIM_CORE
+        assert P.parse_decode_line("FT8", line, 0)["call"] == "K1ABC"
 
 
-def test_tune_on_a_live_demodulator_matches_reference(ref):
+def test_tune_on_a_live_demodulator_matches_reference(oracle, misc):
     """SSBD::Tune(F, isUSB) mid-stream: the oracle's orc_demod_tune against the compiled header, incl. a rejected retune."""
-    fs = 96000
-    iq = ref.synth_iq(3, 64 * 32 * 12, fs, tones_hz=[-20000 + 1000.0, 31000 + 1700.0], amp=9000.0)
-    a, b = ref.Demod(fs, -20000), ref.RefDemod(fs, -20000)
-    n1 = 64 * 32 * 5
-    ya, yb = a.run(iq[:n1]), b.run(iq[:n1])
-    assert np.array_equal(ya.view(np.uint32), yb.view(np.uint32))
-    for obj in (a, b):
-        with pytest.raises(ValueError, match=r"Signal outside of band \(high\)"):
-            obj.tune(45000)                                   # |F + B| > Fs/2: thrown before anything is stored
-    a.tune(31000); b.tune(31000)
-    ya, yb = a.run(iq[n1:]), b.run(iq[n1:])
-    assert np.array_equal(ya.view(np.uint32), yb.view(np.uint32))
-    assert np.array_equal(a.tone.view(np.uint32), b.tone.view(np.uint32))
+    fs, iq, n1, f0, bad, f1 = RC.tune_live_case(oracle)
+    a = oracle.Demod(fs, f0)
+    ya = a.run(iq[:n1])
+    assert np.array_equal(ya.view(np.uint32), misc["tune_live_bits_0"])
+    with pytest.raises(ValueError, match=r"Signal outside of band \(high\)"):
+        a.tune(bad)                                           # |F + B| > Fs/2: thrown before anything is stored
+    assert str(misc["tune_live_error"]) == "Signal outside of band (high)"
+    a.tune(f1)
+    ya = a.run(iq[n1:])
+    assert np.array_equal(ya.view(np.uint32), misc["tune_live_bits_1"])
+    assert np.array_equal(a.tone.view(np.uint32), misc["tune_live_tone_bits"])
     # a retuned object equals a freshly constructed one from that point on (workspace, index and phase are reset)
-    c = ref.Demod(fs, 31000)
+    c = oracle.Demod(fs, f1)
     assert np.array_equal(c.run(iq[n1:]).view(np.uint32), ya.view(np.uint32))
 
 
-def test_tune_without_reset_matches_reference(ref):
+def test_tune_without_reset_matches_reference(oracle, misc):
     """SSBD::Tune(F, isUSB, reset = false) (SSBD.hpp:97,116-121): workspace, index and phase survive the retune.  The oracle's
     orc_demod_tune_ex against the compiled header, bit for bit, through two retunes (one of them flipping the sideband)."""
-    fs = 192000
-    iq = ref.synth_iq(5, 64 * 40 * 9, fs, tones_hz=[-26000 + 900.0, 60000 + 1500.0, 1234 + 700.0], amp=9000.0)
-    a, b = ref.Demod(fs, -26000), ref.RefDemod(fs, -26000)
-    cuts = [0, 64 * 40 * 3, 64 * 40 * 6, 64 * 40 * 9]
-    plan = [None, (60000, True), (1234, False)]
+    fs, iq, f0, cuts, plan = RC.tune_noreset_case(oracle)
+    a = oracle.Demod(fs, f0)
     outs = []
     for k in range(3):
         if plan[k] is not None:
-            a.tune(plan[k][0], plan[k][1], reset=False); b.tune(plan[k][0], plan[k][1], reset=False)
-        ya, yb = a.run(iq[cuts[k]:cuts[k + 1]]), b.run(iq[cuts[k]:cuts[k + 1]])
-        assert np.array_equal(ya.view(np.uint32), yb.view(np.uint32)), k
+            a.tune(plan[k][0], plan[k][1], reset=False)
+        ya = a.run(iq[cuts[k]:cuts[k + 1]])
+        assert np.array_equal(ya.view(np.uint32), misc[f"tune_noreset_bits_{k}"]), k
         outs.append(ya)
     # and it is NOT the reset form: the 31 outputs after the retune still carry the old tuning's partial sums
-    c = ref.Demod(fs, -26000)
+    c = oracle.Demod(fs, f0)
     c.run(iq[:cuts[1]]); c.tune(60000, True, reset=True)
     yc = c.run(iq[cuts[1]:cuts[2]])
     assert not np.array_equal(yc[:31].view(np.uint32), outs[1][:31].view(np.uint32))
