@@ -1392,7 +1392,7 @@ static int push_iq_piece(cwslg_ctx *c, int rx_id, const float *iq, uint32_t n)
 {
     std::shared_ptr<RxStage> stage;
     uint64_t total0 = 0;
-    uint32_t cap = 0;
+    uint32_t cap = 0, iq_len = 1;
     float2 *d_ring = nullptr;
     {
         std::lock_guard<std::mutex> g(c->mu);
@@ -1400,7 +1400,7 @@ static int push_iq_piece(cwslg_ctx *c, int rx_id, const float *iq, uint32_t n)
         int rc = push_prologue(c, rx_id, n, &rx);
         if (rc) return rc;
         stage = rx->stage;
-        total0 = rx->total; cap = rx->cap; d_ring = rx->d_ring;
+        total0 = rx->total; cap = rx->cap; d_ring = rx->d_ring; iq_len = rx->iq_len;
     }
     RxStage &st = *stage;
     hipSetDevice(c->device);
@@ -1433,7 +1433,10 @@ static int push_iq_piece(cwslg_ctx *c, int rx_id, const float *iq, uint32_t n)
         const size_t off_in_half = st.pos % kStageHalf;
         const size_t room = (kStageHalf - off_in_half) / sizeof(float2);
         if (off_in_half == 0 && st.busy[half]) {
-            if (!segs.empty()) break;                       // flush what is staged before waiting for this half to drain
+            // flush what is staged before waiting for this half to drain -- at a whole Receiver block only: what is staged is accounted below through the
+            // frame-overflow guard, block by block from its first sample, and a cut inside a block would pass as a shorter block of its own where the
+            // whole one is dropped (pushes need not be whole blocks, so the staging position need not lie on one)
+            if (!segs.empty() && done % iq_len == 0) break;
             HIPCHK(c, hipEventSynchronize(st.ev[half]));
             st.busy[half] = false;
         }

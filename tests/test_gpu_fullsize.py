@@ -7,12 +7,15 @@ north_star  4096 FT8 slots x 15 s resident on ONE MI355X (94 GB of IQ)
 Every slot's IQ comes from the device-side synthetic source, which is bit-identical to the oracle's generator, so a few
 slots spread over the range are re-derived on the CPU and checked in full: float audio within 1e-5 of frame peak,
 int16 equal up to +-1 LSB rounding ties, FT8/FT4/WSPR/FST4W candidate lists bit-identical to the restatement run on the GPU frame.
-Size-independent properties cover ALL slots: frame counts, valid-sample counts, a finite non-zero scale factor.
+Size-independent properties cover ALL slots: frame counts, valid-sample counts, a finite non-zero scale factor -- and, through
+fused_finalise_check.check_slot, EVERY slot's int16 frame is the finalise of the GPU's own float frame bit for bit (either arithmetic mode), and every
+FT8 slot's spectra plane and candidate list are the restatement's on that frame: the fused finalise of symbol_spectra_v2_kernel, slot by slot.
 """
 import numpy as np
 import pytest
 
 from conftest import assert_frames_match, assert_int16_match
+from fused_finalise_check import SlotJobs, check_slot, spectra_jper
 
 pytestmark = pytest.mark.gpu
 FS, BLK = 192000, 2048
@@ -88,12 +91,21 @@ def _run(ctx, oracle, modes, check, sync=False):
     st = ctx.stats()
     n_emit = sum(int(round(longest / PERIOD[m])) for m in modes)
     assert st["frames_emitted"] == n_emit and st["frames_discarded"] == len(modes) and st["blocks_dropped"] == 0
-    # every slot: a whole frame of the right length came out
-    for rx, ch, mode, f, gs in slots:
-        g = ctx.fetch_frame(ch)
-        per_samples = piece * int(round(PERIOD[mode] / shortest))
-        assert g is not None and g["n_valid"] == per_samples // 16 and len(g["i16"]) == int(12000 * (PERIOD[mode] + 5))
-        assert np.isfinite(g["factor"]) and 0 < g["factor"] < 1e3
+    # every slot: a whole frame of the right length came out, and it is the finalise of the GPU's own float frame bit for bit, zeros from n_valid on; for
+    # FT8 with the sync stage on (the finalise fused into the spectra kernel) the spectra plane and the list are the restatement's on that frame
+    n_ft8 = sum(m == "FT8" for m in modes)
+    sp = dict(lo=200, hi=3000, syncmin=1.5, maxcand=200, jper=spectra_jper(n_ft8)) if sync else None
+    with SlotJobs() as jobs:
+        for rx, ch, mode, f, gs in slots:
+            job = check_slot(ctx, oracle, ch, mode, sp if mode == "FT8" else None, tag=gs)
+            g = job.fetched
+            per_samples = piece * int(round(PERIOD[mode] / shortest))
+            assert g is not None and g["n_valid"] == per_samples // 16 and len(g["i16"]) == int(12000 * (PERIOD[mode] + 5))
+            assert np.isfinite(g["factor"]) and 0 < g["factor"] < 1e3
+            jobs.submit(job)
+            del job, g
+        jobs.drain()
+        assert jobs.done == len(slots)
     # a few slots in full against the oracle
     worst = 0.0
     for k in check:
