@@ -90,6 +90,10 @@ class Ft4Sync(C.Structure):
                 ("ibest", C.c_int32), ("idf", C.c_int32), ("seg", C.c_int32), ("cand", C.c_int32)]
 
 
+class Ft8Soft(C.Structure):
+    _fields_ = [("llr", C.c_float * 174), ("sigma", C.c_float), ("nsync", C.c_int32)]
+
+
 class WsprCandidate(C.Structure):
     _fields_ = [("freq_hz", C.c_float), ("snr_db", C.c_float), ("drift", C.c_float), ("sync", C.c_float), ("shift", C.c_int32)]
 
@@ -129,7 +133,8 @@ ABI_SYMBOLS = [
     "cwslg_set_boundary_rendezvous", "cwslg_set_rendezvous_flag", "cwslg_rccl_unique_id", "cwslg_rccl_init",
     "cwslg_enable_long_sync", "cwslg_fetch_wspr_candidates", "cwslg_fetch_fst4w_candidates", "cwslg_long_sync_debug_fetch",
     "cwslg_synchronize", "cwslg_fetch_frame", "cwslg_fetch_slot", "cwslg_write_wav", "cwslg_fetch_audio_f32", "cwslg_frame_device_ptrs",
-    "cwslg_enable_sync", "cwslg_set_candidate_order", "cwslg_fetch_candidates", "cwslg_set_ft4_syncmin", "cwslg_enable_ft4_coherent", "cwslg_fetch_ft4_sync", "cwslg_sync_debug_fetch", "cwslg_get_stats", "cwslg_reset_stats",
+    "cwslg_enable_sync", "cwslg_set_candidate_order", "cwslg_fetch_candidates", "cwslg_set_ft4_syncmin", "cwslg_enable_ft4_coherent", "cwslg_fetch_ft4_sync",
+    "cwslg_enable_ft8_softbits", "cwslg_fetch_ft8_softbits", "cwslg_sync_debug_fetch", "cwslg_get_stats", "cwslg_reset_stats",
     "cwslg_set_timing", "cwslg_demod_kernel_name", "cwslg_stream", "cwslg_channel_constants", "cwslg_phasor_checkpoint_stride", "cwslg_channel_phasor_checkpoints",
     "cwslg_slot_clock_next", "cwslg_pool_sizing", "cwslg_find_band", "cwslg_parse_decode_line",
     "cwslg_decoder_block_bytes", "cwslg_decoder_block_field", "cwslg_fill_decoder_block", "cwslg_decoder_route", "cwslg_decoder_command",
@@ -215,6 +220,8 @@ def load_library(build_if_missing=True):
     L.cwslg_set_ft4_syncmin.argtypes = [vp, f32]
     L.cwslg_enable_ft4_coherent.argtypes = [vp, i32]
     L.cwslg_fetch_ft4_sync.argtypes = [vp, i32, C.POINTER(Ft4Sync), i32, C.POINTER(i32), C.POINTER(u64)]
+    L.cwslg_enable_ft8_softbits.argtypes = [vp, i32]
+    L.cwslg_fetch_ft8_softbits.argtypes = [vp, i32, C.POINTER(Ft8Soft), i32, C.POINTER(i32), C.POINTER(u64)]
     L.cwslg_sync_debug_fetch.argtypes = [vp, i32, i32, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(i32)]
     L.cwslg_get_stats.argtypes = [vp, C.POINTER(Stats)]
     L.cwslg_reset_stats.argtypes = [vp]
@@ -581,6 +588,24 @@ class Context:
         self._chk(rc)
         return [dict(f0_hz=b.f0_hz, f1_hz=b.f1_hz, dt_s=b.dt_s, sync=b.sync, ibest=b.ibest, idf=b.idf, seg=b.seg, cand=b.cand)
                 for b in buf[:n.value]]
+
+    def enable_ft8_softbits(self, enable=True):
+        """Soft bits per FT8 sync candidate (cwslg_ft8_soft); needs enable_sync; applies from the next boundary on."""
+        self._chk(self.L.cwslg_enable_ft8_softbits(self.h, int(enable)))
+
+    def fetch_ft8_softbits(self, ch, max_cand=600, with_epoch=False):
+        """-> None unless soft-bit records of the channel's current epoch exist, else (llr float32[n, 174], sigma float32[n], nsync int32[n]):
+        row q belongs to entry q of fetch_candidates' list of the same epoch (with_epoch: the frame's start epoch as a fourth item)."""
+        buf = np.zeros((max(int(max_cand), 1), 176), np.float32)          # one 704-byte record per row
+        n = C.c_int()
+        t0 = C.c_uint64()
+        rc = self.L.cwslg_fetch_ft8_softbits(self.h, ch, buf.ctypes.data_as(C.POINTER(Ft8Soft)), int(max_cand), C.byref(n), C.byref(t0))
+        if rc == ERR_NO_FRAME:
+            return None
+        self._chk(rc)
+        rec = buf[:n.value]
+        out = (np.ascontiguousarray(rec[:, :174]), rec[:, 174].copy(), rec[:, 175].copy().view(np.int32))
+        return out + (t0.value,) if with_epoch else out
 
     def enable_long_sync(self, on=True, nfa_hz=1400, nfb_hz=1600, minsync=1.2):
         """Candidate search of the 120 s modes (WSPR: wsprd's front end; FST4W-120: get_candidates_fst4 over nfa..nfb)."""

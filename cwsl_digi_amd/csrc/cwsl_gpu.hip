@@ -46,6 +46,7 @@
 #include "host/spot_parse.hpp"
 #include "sync_kernels.hpp"
 #include "ft4sync_kernels.hpp"
+#include "ft8soft_kernels.hpp"
 #include "longsync_kernels.hpp"
 
 namespace cwslg {
@@ -199,6 +200,7 @@ struct Channel {
     size_t i16_end = ~size_t(0);       // d_i16 holds zeros at and beyond this index (the n_valid of the frame it holds); unknown until the first finalise
     // sync results
     uint64_t cand_t0 = 0;              // start epoch of the frame the candidate lists on the device were computed from (0: none yet)
+    uint64_t soft_t0 = 0;              // ... the FT8 soft-bit records were computed from (cwslg_enable_ft8_softbits; 0: none)
     SyncChannelBuffers syncbuf;
 };
 
@@ -881,10 +883,8 @@ int process_locked(cwslg_ctx *c, bool latency = true)
         HIPCHK(c, upload_workbuf(c, w, kv.second.size() * sizeof(TransWork)));
         const dim3 grid((unsigned)kv.second.size());
         const float *taps = (const float *)c->d_taps[fs];
-        if (D == 16) hipLaunchKernelGGL(demod_transition_kernel<16>, grid, dim3(64), 0, c->stream, (const TransWork *)w->d, taps);
-        else if (D == 8) hipLaunchKernelGGL(demod_transition_kernel<8>, grid, dim3(64), 0, c->stream, (const TransWork *)w->d, taps);
-        else if (D == 4) hipLaunchKernelGGL(demod_transition_kernel<4>, grid, dim3(64), 0, c->stream, (const TransWork *)w->d, taps);
-        else return fail(c, CWSLG_ERR_UNSUPPORTED, "sample rate %u unsupported", fs);
+        if (D != 16 && D != 8 && D != 4) return fail(c, CWSLG_ERR_UNSUPPORTED, "sample rate %u unsupported", fs);
+        hipLaunchKernelGGL(demod_transition_kernel, grid, dim3(64), 0, c->stream, (const TransWork *)w->d, taps, (int)D);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipEventRecord(w->done, c->stream));
         w->in_flight = true;

@@ -946,8 +946,9 @@ __global__ __launch_bounds__(64 * kExact5Waves, 2) void demod_exact5_kernel(cons
 // ---------------------------------------------------------------------------------------------
 // demod_transition_kernel: the (at most 32) outputs after a phase-continuous retune, in ProcessBlock's own order (SSBD.hpp:160-183)
 // whatever the context's mode -- they are a handful per retune.  grid = works, 64 threads: thread = output.
-template <int D>
-__global__ __launch_bounds__(64) void demod_transition_kernel(const TransWork *__restrict__ works, const float *__restrict__ taps)
+// D (the decimation, 16 / 8 / 4) is an argument, not a template parameter: it is only the length of the inner sum, whose order it does not
+// change, and a handful of outputs per retune do not earn one kernel per sample rate in the library's inventory (one kernel per job).
+__global__ __launch_bounds__(64) void demod_transition_kernel(const TransWork *__restrict__ works, const float *__restrict__ taps, int D)
 {
     const TransWork *w = works + blockIdx.x;
     const int o = threadIdx.x;

@@ -138,12 +138,15 @@ int sync_ensure_channel(cwslg_ctx *c, Channel &ch)
     SyncChannelBuffers &b = ch.syncbuf;
     const SyncConfig &cfg = c->sync_cfg;
     const int want_bins = ch.sync_ft4 ? FT4_ROW : cfg.nbins;
-    if (b.d_block && b.nbins == want_bins && b.max_cand == cfg.max_cand && b.ft4 == ch.sync_ft4) return CWSLG_OK;
+    const bool want_soft = cfg.ft8_soft && ch.sync_ft8;      // the soft-bit records exist only while the feature is on (a later enable reallocates)
+    if (b.d_block && b.nbins == want_bins && b.max_cand == cfg.max_cand && b.ft4 == ch.sync_ft4 && (b.d_soft != nullptr) == want_soft) return CWSLG_OK;
     sync_free_channel(b);
+    ch.soft_t0 = 0;
     const size_t sp = ((size_t)(ch.sync_ft4 ? FT4_NHSYM : FT8_NHSYM) * want_bins * sizeof(float) + 255) & ~size_t(255);
     const size_t vec = ((size_t)(FT8_NH1 + 1) * 4 + 255) & ~size_t(255);
     const size_t cand = ((size_t)cfg.max_cand * sizeof(SyncChannelBuffers::Cand) + 255) & ~size_t(255);
-    HIPCHK(c, hipMalloc((void **)&b.d_block, sp + 4 * vec + cand + 256));
+    const size_t soft = want_soft ? (size_t)cfg.max_cand * sizeof(Ft8SoftRec) : 0;
+    HIPCHK(c, hipMalloc((void **)&b.d_block, sp + 4 * vec + cand + 256 + soft));
     char *p = b.d_block;
     b.d_spectra = (float *)p; p += sp;
     b.d_red = (float *)p; p += vec;
@@ -151,7 +154,8 @@ int sync_ensure_channel(cwslg_ctx *c, Channel &ch)
     b.d_jpeak = (int *)p; p += vec;
     b.d_jpeak2 = (int *)p; p += vec;
     b.d_cand = (SyncChannelBuffers::Cand *)p; p += cand;
-    b.d_ncand = (int *)p;
+    b.d_ncand = (int *)p; p += 256;
+    if (want_soft) b.d_soft = (Ft8SoftRec *)p;
     b.nbins = want_bins;
     b.max_cand = cfg.max_cand;
     b.ft4 = ch.sync_ft4;
@@ -168,6 +172,7 @@ int sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
     const SyncConfig &cfg = c->sync_cfg;
     std::vector<SyncWork> works8, works4;
     std::vector<Ft4Work> works4c;
+    std::vector<Ft8SoftRec *> soft8;                          // cwslg_enable_ft8_softbits: one record array per FT8 channel, in works8's order
     for (int id : emitted) {
         Channel &ch = c->chans[id];
         if (!ch.sync_ft8 && !ch.sync_ft4) continue;
@@ -182,6 +187,10 @@ int sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
         if (ch.fin_fused) { w.fin = ch.fused_fin; ch.fin_fused = false; }       // the spectra kernel finalises this frame first (boundary_locked)
         (ch.sync_ft8 ? works8 : works4).push_back(w);
         ch.cand_t0 = ch.frame_t0;     // the lists now queued belong to this frame
+        if (ch.sync_ft8 && cfg.ft8_soft) {
+            soft8.push_back(ch.syncbuf.d_soft);
+            ch.soft_t0 = ch.frame_t0;                         // ... and so do the soft-bit records (a boundary with the feature off leaves the OLD epoch: nothing to fetch)
+        }
         if (ch.sync_ft4 && cfg.ft4_coherent) {
             if ((rc = ft4c_ensure_tables(c)) != CWSLG_OK || (rc = ft4c_ensure_channel(c, ch)) != CWSLG_OK) return rc;
             Ft4Work f{};
@@ -193,11 +202,21 @@ int sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
     }
     if (works8.empty() && works4.empty()) return CWSLG_OK;
     const size_t n8 = works8.size(), n4 = works4.size();
-    WorkBuf *wb = acquire_workbuf(c, (n8 + n4) * sizeof(SyncWork));
+    // the soft-bit launch's record pointers ride behind the descriptors in the same buffer (nothing is added while the feature is off)
+    const size_t wb_bytes = (n8 + n4) * sizeof(SyncWork) + soft8.size() * sizeof(Ft8SoftRec *);
+    WorkBuf *wb = acquire_workbuf(c, wb_bytes);
     if (!wb) return fail(c, CWSLG_ERR_NOMEM, "work buffer allocation failed");
     if (n8) std::memcpy(wb->h, works8.data(), n8 * sizeof(SyncWork));
     if (n4) std::memcpy((SyncWork *)wb->h + n8, works4.data(), n4 * sizeof(SyncWork));
-    HIPCHK(c, upload_workbuf(c, wb, (n8 + n4) * sizeof(SyncWork)));
+    if (!soft8.empty()) std::memcpy((SyncWork *)wb->h + n8 + n4, soft8.data(), soft8.size() * sizeof(Ft8SoftRec *));
+    HIPCHK(c, upload_workbuf(c, wb, wb_bytes));
+    // one wave per candidate behind whichever search form wrote d_cand / d_ncand (the count is read on the device); its time is part of the
+    // stage's span (stats.sync_ms), not of the search's own
+    auto launch_soft = [&](hipStream_t st) {
+        if (soft8.empty()) return;
+        hipLaunchKernelGGL(ft8_softbits_kernel, dim3((unsigned)((cfg.max_cand + FT8S_WAVES - 1) / FT8S_WAVES), (unsigned)n8), dim3(64 * FT8S_WAVES), 0, st,
+                           (const SyncWork *)wb->d, (Ft8SoftRec *const *)((const SyncWork *)wb->d + n8 + n4), cfg.nbins, cfg.max_cand);
+    };
     WorkBuf *wb4 = nullptr;
     if (!works4c.empty()) {
         wb4 = acquire_workbuf(c, works4c.size() * sizeof(Ft4Work));
@@ -278,6 +297,7 @@ int sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
             hipLaunchKernelGGL(ft8_candidates_kernel<1024>, dim3((unsigned)n8), dim3(1024), 0, s8, d8, cfg.ia, cfg.ib, cfg.syncmin, cfg.max_cand, cfg.order);
         }
         span_end(c, qb);
+        launch_soft(s8);
 #if CWSLG_LAB
         } else {
         // the three-launch forms (one workgroup per 32-bin band, then one per channel for the selection), all with the same bits:
@@ -303,6 +323,7 @@ int sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
         else
             hipLaunchKernelGGL(ft8_candidates_kernel<1024>, dim3((unsigned)n8), dim3(1024), 0, cs, d8, cfg.ia, cfg.ib,
                                cfg.syncmin, cfg.max_cand, cfg.order);
+        launch_soft(cs);
         if (cand_async) {
             if (sb) hipEventRecord(sb, c->side);
             HIPCHK(c, hipEventRecord(c->cand_done, c->side));
@@ -387,6 +408,8 @@ int cwslg_enable_sync(cwslg_ctx *c, int enable, float syncmin, int max_cand, int
         if (cfg.ib + 12 > FT8_NH1) cfg.ib = FT8_NH1 - 12;
         if (cfg.ib < cfg.ia) return fail(c, CWSLG_ERR_ARG, "empty sync frequency range");
         cfg.nbins = (cfg.ib + 13 + 31) / 32 * 32;   // row pitch = whole 128-byte lines (ft8_sync_chan_kernel fetches one line per band and step)
+        cfg.ft8_soft = c->sync_cfg.ft8_soft;
+        if (cfg.ft8_soft) cfg.nbins = (cfg.ib + 15 + 31) / 32 * 32;   // soft bits on: tone 7 of bin ib (ib + 14) lies inside the row
         hipSetDevice(c->device);
         cfg.ft4_coherent = c->sync_cfg.ft4_coherent;
         cfg.order = c->sync_cfg.order;
@@ -447,6 +470,55 @@ int cwslg_fetch_candidates(cwslg_ctx *c, int ch_id, cwslg_candidate *dst, int ma
     HIPCHK(c, hipStreamSynchronize(rf.fs));
     cnt = std::max(0, std::min(cnt, lim));
     if (cnt > 0) std::memcpy(dst, tmp.data(), (size_t)cnt * sizeof(cwslg_candidate));
+    *n = cnt;
+    return CWSLG_OK;
+}
+
+// FT8 soft bits (ft8soft_kernels.hpp).  The records are handed out like the lists, and only together with them: a fetch needs the records, the
+// list and the frame to be of ONE epoch (soft_t0 == cand_t0 == frame_t0) -- after a boundary that ran with the feature off there is nothing to
+// fetch, never an older slot's records under the newer epoch.
+int cwslg_enable_ft8_softbits(cwslg_ctx *c, int enable)
+{
+    if (!c) return CWSLG_ERR_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    if (enable && !c->sync_cfg.enabled) return fail(c, CWSLG_ERR_ARG, "FT8 soft bits need the sync stage (cwslg_enable_sync)");
+    SyncConfig &cfg = c->sync_cfg;
+    cfg.ft8_soft = enable != 0;
+    // the row pitch: ib + 13 as ever while the feature is off; ib + 15 while it is on (channels reallocate at their next boundary)
+    cfg.nbins = (cfg.ib + (cfg.ft8_soft ? 15 : 13) + 31) / 32 * 32;
+    return CWSLG_OK;
+}
+
+int cwslg_fetch_ft8_softbits(cwslg_ctx *c, int ch_id, cwslg_ft8_soft *dst, int max, int *n, uint64_t *start_epoch)
+{
+    if (!c || !n || (max > 0 && !dst)) return CWSLG_ERR_ARG;
+    *n = 0;
+    const Ft8SoftRec *src = nullptr;
+    const int *cnt_src = nullptr;
+    int lim = 0;
+    ResultFetch rf;
+    {
+        std::lock_guard<std::mutex> g(c->mu);
+        if (ch_id < 0 || ch_id >= (int)c->chans.size() || !c->chans[ch_id].open) return fail(c, CWSLG_ERR_ARG, "bad channel id");
+        Channel &ch = c->chans[ch_id];
+        if (!ch.sync_ft8) return fail(c, CWSLG_ERR_MODE, "soft bits exist for FT8 channels only (mode %s)", ch.mode.c_str());
+        if (!ch.have_frame || !ch.syncbuf.d_block || !ch.syncbuf.d_soft || !ch.soft_t0 || ch.soft_t0 != ch.frame_t0 || ch.soft_t0 != ch.cand_t0)
+            return CWSLG_ERR_NO_FRAME;
+        hipSetDevice(c->device);
+        if (start_epoch) *start_epoch = ch.soft_t0;
+        src = ch.syncbuf.d_soft; cnt_src = ch.syncbuf.d_ncand; lim = std::min(std::max(max, 0), ch.syncbuf.max_cand);
+        int rc = begin_result_fetch(c, ch, rf);
+        if (rc) return rc;
+    }
+    static_assert(sizeof(cwslg_ft8_soft) == sizeof(Ft8SoftRec), "record layout");
+    int cnt = 0;
+    std::vector<Ft8SoftRec> tmp((size_t)lim);
+    HIPCHK(c, hipStreamWaitEvent(rf.fs, rf.ev, 0));
+    HIPCHK(c, hipMemcpyAsync(&cnt, cnt_src, sizeof(int), hipMemcpyDeviceToHost, rf.fs));
+    if (lim > 0) HIPCHK(c, hipMemcpyAsync(tmp.data(), src, (size_t)lim * sizeof(Ft8SoftRec), hipMemcpyDeviceToHost, rf.fs));
+    HIPCHK(c, hipStreamSynchronize(rf.fs));
+    cnt = std::max(0, std::min(cnt, lim));
+    if (cnt > 0) std::memcpy(dst, tmp.data(), (size_t)cnt * sizeof(Ft8SoftRec));
     *n = cnt;
     return CWSLG_OK;
 }

@@ -43,6 +43,7 @@ struct SyncConfig {
     int order = 0;                        // cwslg_set_candidate_order: 0 strongest first (cut at max_cand in that order), 1 ascending frequency (cut in THAT order)
     int f_lo_hz = 200, f_hi_hz = 3000;
     int ia = 64, ib = 960, nbins = 976;   // derived: bin range and stored row length (ib+13 rounded up to 16)
+    bool ft8_soft = false;                // cwslg_enable_ft8_softbits: soft bits per FT8 candidate (ft8soft_kernels.hpp); the row then holds tone 7 of bin ib (ib+15 rounded up)
 };
 
 struct SyncTables {                       // device pointers: W_NZ, W_128, 0.5 W_2NZ twiddles, optional window
@@ -66,6 +67,7 @@ struct SyncChannelBuffers {
     int *d_jpeak = nullptr, *d_jpeak2 = nullptr;    // [NH1+1]
     struct Cand { int freq_bin, time_step; float sync, freq_hz, dt_s; } *d_cand = nullptr;   // [max_cand]
     int *d_ncand = nullptr;
+    struct Ft8SoftRec *d_soft = nullptr;  // [max_cand], FT8 channels while cwslg_enable_ft8_softbits is on (part of d_block)
     int nbins = 0, max_cand = 0;
     bool ft4 = false;                     // FT4 layout: spectra [122][FT4_ROW]; red = normalised savsm, red2 = sbase
     // FT4 coherent sync (ft4sync_kernels.hpp): frame spectrum, its stage-A scratch, refined records

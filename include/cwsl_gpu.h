@@ -388,6 +388,35 @@ typedef struct {
 } cwslg_ft4_sync;
 int cwslg_enable_ft4_coherent(cwslg_ctx *ctx, int enable);
 int cwslg_fetch_ft4_sync(cwslg_ctx *ctx, int ch_id, cwslg_ft4_sync *dst, int max, int *n, uint64_t *start_epoch);
+/* FT8 soft bits (row a13; PARITY UNPINNED, restated from upstream ft8b's nsym = 1 pass: its s8 magnitudes, the hard-decision Costas count
+ * nsync, bmeta, normalizebmet, scalefac = 2.83).  One record per entry of the FT8 candidate list of the SAME epoch (record q belongs to entry q),
+ * computed on the device from the symbol-spectra plane the search has just read, ON THE PLANE'S GRID -- one step (40 ms) by one bin (3.125 Hz),
+ * the way ft8_lib decodes from its waterfall; this is not ft8b's 192 000-point downsample with its fine time / frequency search.  A consumer
+ * (an in-process LDPC decoder, a pre-filter ahead of jt9 -- ft8b rejects nsync <= 6 --, a quality figure per spot) gets this without pulling the
+ * 1.45 MB plane of every slot back to the host.  Off by default; while it is off nothing changes (launches, buffers, row pitch, lists).
+ *   Addressing: i = freq_bin, j = time_step of the candidate; S(bin, m) the plane, m the 1-based step.  Symbol n = 0..78 sits at step
+ *       m = j + 12 + 4 n, tone k = 0..7 at bin i + 2 k.
+ *   Magnitudes: s8[n][k] = sqrtf(S(i + 2 k, m)), correctly rounded; 0 where m < 1, m > 372 or the bin is above 1920.
+ *   nsync: over the 21 Costas symbols n = base + r (base 0, 36, 72; r = 0..6) the number whose FIRST maximum over k of s8[n][k] (ties to the
+ *       lowest k, Fortran maxloc) is at k = icos7[r], icos7 = 3,1,4,0,6,5,2.
+ *   Bit metrics: the 58 data symbols in the order n = 7..35, 43..71; graymap = 0,1,3,2,5,6,4,7, s2[v] = s8[n][graymap[v]]; three per symbol, MSB
+ *       first, exact float32 max and subtract:
+ *           b[p]   = max(s2[4..7])     - max(s2[0..3])
+ *           b[p+1] = max(s2[2,3,6,7])  - max(s2[0,1,4,5])
+ *           b[p+2] = max(s2[1,3,5,7])  - max(s2[0,2,4,6])
+ *   Normalisation (normalizebmet), every operation un-fused float32, the sums in the order a 64-lane wave evaluates them: pad b to 192 entries
+ *       with +0; a[l] = (b[l] + b[l+64]) + b[l+128], l = 0..63; six halving steps a[l] = a[l] + a[l+h] for l < h, h = 32, 16, 8, 4, 2, 1;
+ *       S1 = a[0]; S2 the same tree over fl(b b); mean = S1 / 174.0f, m2 = S2 / 174.0f, var = m2 - fl(mean mean);
+ *       sigma = sqrtf(var > 0 ? var : m2); llr[t] = fl(fl(b[t] / sigma) 2.83f), every llr +0 if sigma == 0.  llr > 0 means bit 1.
+ *   Row pitch: tone 7 of a candidate at the upper edge bin ib lies at ib + 14, so while the feature is on the plane's row pitch
+ *       (cwslg_sync_debug_fetch's row_len) is ib + 15 rounded up to 32 bins instead of ib + 13 (the default f_hi = 3000: 992 either way).
+ * cwslg_enable_ft8_softbits needs the sync stage enabled (CWSLG_ERR_ARG otherwise) and applies from the next boundary on.
+ * cwslg_fetch_ft8_softbits hands the records out like cwslg_fetch_candidates (same ticket, same count: min(list length, max)); it returns
+ * CWSLG_ERR_MODE for a channel of another mode and CWSLG_ERR_NO_FRAME unless records, list and frame belong to one epoch -- after a boundary
+ * that ran with the feature off there is nothing to fetch, never an older slot's records under the newer epoch. */
+typedef struct { float llr[174]; float sigma; int32_t nsync; } cwslg_ft8_soft;   /* 704 bytes */
+int cwslg_enable_ft8_softbits(cwslg_ctx *ctx, int enable);
+int cwslg_fetch_ft8_softbits(cwslg_ctx *ctx, int ch_id, cwslg_ft8_soft *dst, int max, int *n, uint64_t *start_epoch);
 int cwslg_fetch_slot(cwslg_ctx *ctx, int ch_id, int16_t *frame, size_t cap, void *list, size_t list_bytes,
                      cwslg_ft4_sync *ft4, int max_ft4, cwslg_slot_result *out);
 int cwslg_set_ft4_syncmin(cwslg_ctx *ctx, float syncmin);

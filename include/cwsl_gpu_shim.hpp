@@ -54,6 +54,8 @@ public:
     // SyncPredicate::store(true) for a whole group (CWSL_DIGI.cpp:247-251)
     void slotBoundary(int group, std::uint64_t epoch_s) { check(c_, cwslg_slot_boundary(c_, group, epoch_s)); }
     void process() { check(c_, cwslg_process(c_)); }
+    // soft bits per FT8 sync candidate from the next boundary on (needs the sync stage: cwslg_enable_sync) -- SsbChannel::fetchFt8Softbits
+    void enableFt8Softbits(bool enable = true) { check(c_, cwslg_enable_ft8_softbits(c_, enable ? 1 : 0)); }
     void synchronize() { check(c_, cwslg_synchronize(c_)); }
     // One block for each of several receivers in ONE call (cwslg_push_iq_many): for a host that serves thousands of streams, where a
     // per-receiver push per block (Receiver.hpp:242-249, ReceiverPort::push below) would mean hundreds of thousands of copies a second.
@@ -167,6 +169,18 @@ public:
         out.resize(max);
         int n = 0;
         const int rc = cwslg_fetch_ft4_sync(ctx_.raw(), id_, out.data(), max, &n, nullptr);
+        if (rc == CWSLG_ERR_NO_FRAME) { out.clear(); return 0; }
+        check(ctx_.raw(), rc);
+        out.resize(n);
+        return n;
+    }
+    // FT8 channels with Context::enableFt8Softbits: record q (174 bit metrics, sigma, nsync) belongs to entry q of candidates() of the same
+    // epoch -- cwslg_fetch_ft8_softbits; 0 records while none of the current epoch exist
+    int fetchFt8Softbits(std::vector<cwslg_ft8_soft> &out, int max = 600, std::uint64_t *startEpoch = nullptr)
+    {
+        out.resize(max);
+        int n = 0;
+        const int rc = cwslg_fetch_ft8_softbits(ctx_.raw(), id_, out.data(), max, &n, startEpoch);
         if (rc == CWSLG_ERR_NO_FRAME) { out.clear(); return 0; }
         check(ctx_.raw(), rc);
         out.resize(n);
