@@ -94,6 +94,10 @@ class Ft8Soft(C.Structure):
     _fields_ = [("llr", C.c_float * 174), ("sigma", C.c_float), ("nsync", C.c_int32)]
 
 
+class Ft4Soft(C.Structure):
+    _fields_ = [("llr", (C.c_float * 174) * 3), ("sigma", C.c_float * 3), ("nsync", C.c_int32), ("nqual", C.c_int32), ("pad_", C.c_int32)]
+
+
 class WsprCandidate(C.Structure):
     _fields_ = [("freq_hz", C.c_float), ("snr_db", C.c_float), ("drift", C.c_float), ("sync", C.c_float), ("shift", C.c_int32)]
 
@@ -134,7 +138,7 @@ ABI_SYMBOLS = [
     "cwslg_enable_long_sync", "cwslg_fetch_wspr_candidates", "cwslg_fetch_fst4w_candidates", "cwslg_long_sync_debug_fetch",
     "cwslg_synchronize", "cwslg_fetch_frame", "cwslg_fetch_slot", "cwslg_write_wav", "cwslg_fetch_audio_f32", "cwslg_frame_device_ptrs",
     "cwslg_enable_sync", "cwslg_set_candidate_order", "cwslg_fetch_candidates", "cwslg_set_ft4_syncmin", "cwslg_enable_ft4_coherent", "cwslg_fetch_ft4_sync",
-    "cwslg_enable_ft8_softbits", "cwslg_fetch_ft8_softbits", "cwslg_sync_debug_fetch", "cwslg_get_stats", "cwslg_reset_stats",
+    "cwslg_enable_ft8_softbits", "cwslg_fetch_ft8_softbits", "cwslg_enable_ft4_softbits", "cwslg_fetch_ft4_softbits", "cwslg_sync_debug_fetch", "cwslg_get_stats", "cwslg_reset_stats",
     "cwslg_set_timing", "cwslg_demod_kernel_name", "cwslg_stream", "cwslg_channel_constants", "cwslg_phasor_checkpoint_stride", "cwslg_channel_phasor_checkpoints",
     "cwslg_slot_clock_next", "cwslg_pool_sizing", "cwslg_find_band", "cwslg_parse_decode_line",
     "cwslg_decoder_block_bytes", "cwslg_decoder_block_field", "cwslg_fill_decoder_block", "cwslg_decoder_route", "cwslg_decoder_command",
@@ -222,6 +226,8 @@ def load_library(build_if_missing=True):
     L.cwslg_fetch_ft4_sync.argtypes = [vp, i32, C.POINTER(Ft4Sync), i32, C.POINTER(i32), C.POINTER(u64)]
     L.cwslg_enable_ft8_softbits.argtypes = [vp, i32]
     L.cwslg_fetch_ft8_softbits.argtypes = [vp, i32, C.POINTER(Ft8Soft), i32, C.POINTER(i32), C.POINTER(u64)]
+    L.cwslg_enable_ft4_softbits.argtypes = [vp, i32]
+    L.cwslg_fetch_ft4_softbits.argtypes = [vp, i32, C.POINTER(Ft4Soft), i32, C.POINTER(i32), C.POINTER(u64)]
     L.cwslg_sync_debug_fetch.argtypes = [vp, i32, i32, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(i32)]
     L.cwslg_get_stats.argtypes = [vp, C.POINTER(Stats)]
     L.cwslg_reset_stats.argtypes = [vp]
@@ -605,6 +611,26 @@ class Context:
         self._chk(rc)
         rec = buf[:n.value]
         out = (np.ascontiguousarray(rec[:, :174]), rec[:, 174].copy(), rec[:, 175].copy().view(np.int32))
+        return out + (t0.value,) if with_epoch else out
+
+    def enable_ft4_softbits(self, enable=True):
+        """Soft bits per refined FT4 sync record (cwslg_ft4_soft); needs enable_sync; applies from the next boundary on."""
+        self._chk(self.L.cwslg_enable_ft4_softbits(self.h, int(enable)))
+
+    def fetch_ft4_softbits(self, ch, max_rec=1800, with_epoch=False):
+        """-> None unless soft-bit records of the channel's current epoch exist, else (llr float32[n, 3, 174], sigma float32[n, 3],
+        nsync int32[n], nqual int32[n]): row q belongs to entry q of fetch_ft4_sync of the same epoch (with_epoch: the frame's start epoch
+        as a fifth item)."""
+        buf = np.zeros((max(int(max_rec), 1), 528), np.float32)           # one 2112-byte record per row
+        n = C.c_int()
+        t0 = C.c_uint64()
+        rc = self.L.cwslg_fetch_ft4_softbits(self.h, ch, buf.ctypes.data_as(C.POINTER(Ft4Soft)), int(max_rec), C.byref(n), C.byref(t0))
+        if rc == ERR_NO_FRAME:
+            return None
+        self._chk(rc)
+        rec = buf[:n.value]
+        out = (np.ascontiguousarray(rec[:, :522]).reshape(-1, 3, 174), np.ascontiguousarray(rec[:, 522:525]),
+               rec[:, 525].copy().view(np.int32), rec[:, 526].copy().view(np.int32))
         return out + (t0.value,) if with_epoch else out
 
     def enable_long_sync(self, on=True, nfa_hz=1400, nfb_hz=1600, minsync=1.2):

@@ -47,6 +47,7 @@
 #include "sync_kernels.hpp"
 #include "ft4sync_kernels.hpp"
 #include "ft8soft_kernels.hpp"
+#include "ft4soft_kernels.hpp"
 #include "longsync_kernels.hpp"
 
 namespace cwslg {
@@ -201,6 +202,7 @@ struct Channel {
     // sync results
     uint64_t cand_t0 = 0;              // start epoch of the frame the candidate lists on the device were computed from (0: none yet)
     uint64_t soft_t0 = 0;              // ... the FT8 soft-bit records were computed from (cwslg_enable_ft8_softbits; 0: none)
+    uint64_t soft4_t0 = 0;             // ... the FT4 soft-bit records were computed from (cwslg_enable_ft4_softbits; 0: none)
     SyncChannelBuffers syncbuf;
 };
 

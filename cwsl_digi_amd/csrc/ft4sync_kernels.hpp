@@ -259,21 +259,31 @@ __device__ __forceinline__ float f4_sync4d(const F4Cd &cd, int i0, const float2 
     return ((f4_pmag(z1) + f4_pmag(z2)) + f4_pmag(z3)) + f4_pmag(z4);
 }
 
-__global__ __launch_bounds__(256) void ft4_refine_kernel(const Ft4Work *__restrict__ works, Ft4Tables tb, int max_cand)
+// LDS of one candidate's baseband: what ft4_refine_kernel and ft4_softbits_kernel (ft4soft_kernels.hpp) both build.  The arrays are the
+// kernels' own __shared__ variables (declared by F4_BASE_LDS, handed over as pointers): one struct would fix their layout and was measured
+// 5 % slower for the refinement stage.
+struct F4BaseLds {
+    float2 (*y)[64];                   // [63][64] stage-A output / FFT rows (free once the baseband stands)
+    float2 (*cd)[F4C_PLANE];           // [4][F4C_PLANE]
+    float2 (*c1)[64];                  // [10][64]
+    float2 *w63;                       // [63]
+    float2 *w64;                       // [32]
+    float *part;                       // [256]
+};
+#define F4_BASE_LDS(L)                                                                                                     \
+    __shared__ float2 s_y[63][64];                                                                                         \
+    __shared__ float2 s_cd[4][F4C_PLANE];                                                                                  \
+    __shared__ float2 s_c1[10][64];                                                                                        \
+    __shared__ float2 s_w63[63];                                                                                           \
+    __shared__ float2 s_w64[32];                                                                                           \
+    __shared__ float s_part[256];                                                                                          \
+    const F4BaseLds L{s_y, s_cd, s_c1, s_w63, s_w64, s_part}
+
+// orc_ft4_downsample at f0: the 630 windowed bins around lroundf(f0 / df) -> inverse 4032 = 63 x 64 transform -> unit-mean-power baseband in
+// L.cd (four planes by sample index mod 4).  Called by all 256 threads of the workgroup; ends behind a barrier.
+__device__ __forceinline__ void f4_baseband(const F4BaseLds &L, const Ft4Work *w, const Ft4Tables &tb, float f0, int tid)
 {
-    __shared__ float2 s_y[63][64];                 // stage-A output / FFT rows; afterwards the 9 tweaked reference sets
-    __shared__ float2 s_cd[4][F4C_PLANE];
-    __shared__ float2 s_c1[10][64];
-    __shared__ float2 s_w63[63];
-    __shared__ float2 s_w64[32];
-    __shared__ float s_part[256];
-    __shared__ unsigned long long s_key[4];
-    const Ft4Work *w = works + blockIdx.y;
-    const int cand = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    int ncand = *as_global(w->ncand);
-    if (ncand > max_cand) ncand = max_cand;
-    if (cand >= ncand) return;                      // workgroup-uniform
-    const float f0 = as_global(w->cand)[cand].freq_hz;
+    const int lane = tid & 63, wv = tid >> 6;
     const float df = 12000.0f / (float)F4C_NMAX;
     const int i0 = (int)lroundf(f0 / df);
 
@@ -290,10 +300,10 @@ __global__ __launch_bounds__(256) void ft4_refine_kernel(const Ft4Work *__restri
             const float wk = tb.win[k - F4C_KLO];
             v = make_float2((x.x * wk) / 4032.0f, (x.y * wk) / 4032.0f);
         }
-        s_c1[q][b] = v;
+        L.c1[q][b] = v;
     }
-    if (tid < 63) s_w63[tid] = tb.w63[tid];
-    if (tid >= 64 && tid < 96) s_w64[tid - 64] = tb.w64[tid - 64];
+    if (tid < 63) L.w63[tid] = tb.w63[tid];
+    if (tid >= 64 && tid < 96) L.w64[tid - 64] = tb.w64[tid - 64];
     __syncthreads();
     // ---- stage A: 63-point inverse DFT over the 10 live rows, twiddle conj(W4032^(bc)), bit-reversed store
     {
@@ -303,11 +313,11 @@ __global__ __launch_bounds__(256) void ft4_refine_kernel(const Ft4Work *__restri
 #pragma unroll
             for (int q = 0; q < 10; ++q) {
                 const int a = (q < 8) ? q : 53 + q;
-                const float2 z = s_c1[q][b], t = s_w63[(a * c) % 63];
+                const float2 z = L.c1[q][b], t = L.w63[(a * c) % 63];
                 yr = __builtin_fmaf(z.x, t.x, yr); yr = __builtin_fmaf(z.y, t.y, yr);
                 yi = __builtin_fmaf(z.y, t.x, yi); yi = __builtin_fmaf(-z.x, t.y, yi);
             }
-            s_y[c][rev6(b)] = cmulc_f(make_float2(yr, yi), tb.w4032[c * 64 + b]);
+            L.y[c][rev6(b)] = cmulc_f(make_float2(yr, yi), tb.w4032[c * 64 + b]);
         }
     }
     wave_sync_lds();                                 // rows c = wv, wv+4, ... were written by this wave only
@@ -315,42 +325,53 @@ __global__ __launch_bounds__(256) void ft4_refine_kernel(const Ft4Work *__restri
     for (int len = 2; len <= 64; len <<= 1) {
         for (int i = 0; i < 8; ++i) {
             const int ra = wv + 8 * i, rb = wv + 8 * i + 4;     // rows of lanes 0-31 / 32-63
-            if (rb < 63) fft64_stage<true>(s_y[ra], s_y[rb], s_w64, len, lane);
-            else if (ra < 63 && lane < 32) fft64_stage<true>(s_y[ra], s_y[ra], s_w64, len, lane);
+            if (rb < 63) fft64_stage<true>(L.y[ra], L.y[rb], L.w64, len, lane);
+            else if (ra < 63 && lane < 32) fft64_stage<true>(L.y[ra], L.y[ra], L.w64, len, lane);
         }
         wave_sync_lds();
     }
     __syncthreads();
     // ---- cd[m] = y[m % 63][m / 63]; mean power by 256 strided partial sums and a halving tree; normalise
-    {
-        float s = 0.f;
-        for (int m = tid; m < F4C_NP; m += 256) {
-            const float2 v = s_y[m % 63][m / 63];
-            s_cd[m & 3][m >> 2] = v;
-            s = __builtin_fmaf(v.x, v.x, __builtin_fmaf(v.y, v.y, s));
-        }
-        s_part[tid] = s;
-        __syncthreads();
-        for (int h = 128; h >= 1; h >>= 1) {
-            if (tid < h) s_part[tid] = s_part[tid] + s_part[tid + h];
-            __syncthreads();
-        }
-        const float sum2 = s_part[0] / 4032.0f;
-        if (sum2 > 0.0f) {
-            const float sc = sqrtf(sum2);
-            for (int m = tid; m < F4C_NP; m += 256) {
-                float2 v = s_cd[m & 3][m >> 2];
-                v.x = v.x / sc; v.y = v.y / sc;
-                s_cd[m & 3][m >> 2] = v;
-            }
-        }
-        __syncthreads();
-        if (cand == 0 && w->cd_dbg)
-            for (int m = tid; m < F4C_NP; m += 256) gst2(w->cd_dbg + m, s_cd[m & 3][m >> 2]);
+    float s = 0.f;
+    for (int m = tid; m < F4C_NP; m += 256) {
+        const float2 v = L.y[m % 63][m / 63];
+        L.cd[m & 3][m >> 2] = v;
+        s = __builtin_fmaf(v.x, v.x, __builtin_fmaf(v.y, v.y, s));
     }
+    L.part[tid] = s;
+    __syncthreads();
+    for (int h = 128; h >= 1; h >>= 1) {
+        if (tid < h) L.part[tid] = L.part[tid] + L.part[tid + h];
+        __syncthreads();
+    }
+    const float sum2 = L.part[0] / 4032.0f;
+    if (sum2 > 0.0f) {
+        const float sc = sqrtf(sum2);
+        for (int m = tid; m < F4C_NP; m += 256) {
+            float2 v = L.cd[m & 3][m >> 2];
+            v.x = v.x / sc; v.y = v.y / sc;
+            L.cd[m & 3][m >> 2] = v;
+        }
+    }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(256) void ft4_refine_kernel(const Ft4Work *__restrict__ works, Ft4Tables tb, int max_cand)
+{
+    F4_BASE_LDS(L);                                 // L.y: afterwards the 9 tweaked reference sets
+    __shared__ unsigned long long s_key[4];
+    const Ft4Work *w = works + blockIdx.y;
+    const int cand = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    int ncand = *as_global(w->ncand);
+    if (ncand > max_cand) ncand = max_cand;
+    if (cand >= ncand) return;                      // workgroup-uniform
+    const float f0 = as_global(w->cand)[cand].freq_hz;
+    f4_baseband(L, w, tb, f0, tid);
+    if (cand == 0 && w->cd_dbg)
+        for (int m = tid; m < F4C_NP; m += 256) gst2(w->cd_dbg + m, L.cd[m & 3][m >> 2]);
     // ---- the search of ft4_decode: 3 segments x (coarse, fine)
-    F4Cd cd{s_cd};
-    float2 *s_cs = &s_y[0][0];                       // [9][256] tweaked references (s_y is free now)
+    F4Cd cd{L.cd};
+    float2 *s_cs = &L.y[0][0];                       // [9][256] tweaked references (L.y is free now)
     float smax = -99.0f, smax1 = 0.0f;
     int nrec = 0;
     for (int iseg = 1; iseg <= 3; ++iseg) {

@@ -63,7 +63,7 @@ int ft4c_ensure_tables(cwslg_ctx *c)
     auto mk = [](double co, double si) { return make_float2((float)co, (float)si); };
     std::vector<float2> t;
     const size_t o567 = 0, on2 = o567 + F4C_NA, o2n = on2 + F4C_N2, o64 = o2n + F4C_N2 + 1, o63 = o64 + 32, o4032 = o63 + 63,
-                 ocs = o4032 + F4C_NP, otw = ocs + 256, total = otw + 33 * 64;
+                 ocs = o4032 + F4C_NP, otw = ocs + 256, o32 = otw + 33 * 64, total = o32 + 32;
     t.resize(total);
     for (int k = 0; k < F4C_NA; ++k) t[o567 + k] = mk(std::cos(2.0 * pi * k / 567.0), -std::sin(2.0 * pi * k / 567.0));
     for (int k = 0; k < F4C_N2; ++k) t[on2 + k] = mk(std::cos(2.0 * pi * k / 36288.0), -std::sin(2.0 * pi * k / 36288.0));
@@ -98,6 +98,9 @@ int ft4c_ensure_tables(cwslg_ctx *c)
             const double a = 2.0 * pi * (double)d * (double)(k + 1) * 36.0 / 12000.0;
             t[otw + (d + 16) * 64 + k] = (d == 0) ? mk(1.0, 0.0) : mk(std::cos(a), std::sin(a));
         }
+    // the soft-bit stage's symbol spectra (ft4soft_kernels.hpp): exp(+2 pi i p / 32), cardinal points exact as in csync
+    for (int p = 0; p < 32; ++p) t[o32 + p] = mk(std::cos(2.0 * pi * p / 32.0), std::sin(2.0 * pi * p / 32.0));
+    t[o32] = mk(1.0, 0.0); t[o32 + 8] = mk(0.0, 1.0); t[o32 + 16] = mk(-1.0, 0.0); t[o32 + 24] = mk(0.0, -1.0);
     std::vector<float> win(F4C_KHI - F4C_KLO + 1);
     for (int k = F4C_KLO; k <= F4C_KHI; ++k) {
         const int i = k + 126;
@@ -112,6 +115,7 @@ int ft4c_ensure_tables(cwslg_ctx *c)
     HIPCHK(c, hipMemcpy(c->sync_shared.d_ft4c_win, win.data(), win.size() * sizeof(float), hipMemcpyHostToDevice));
     const float2 *b = c->sync_shared.d_ft4c;
     c->ft4_tables = Ft4Tables{b + o567, b + on2, b + o2n, b + o64, b + o63, b + o4032, b + ocs, b + otw, c->sync_shared.d_ft4c_win};
+    c->sync_shared.ft4_w32 = b + o32;
     return CWSLG_OK;
 }
 
@@ -133,6 +137,18 @@ int ft4c_ensure_channel(cwslg_ctx *c, Channel &ch)
     return CWSLG_OK;
 }
 
+// The FT4 soft-bit records (ft4soft_kernels.hpp), [max_cand][3] in d_rec's slot layout: they exist only while the feature is on (a boundary
+// with it off frees them), go with the channel (sync_free_channel) and follow max_cand (sync_ensure_channel frees everything when it changes).
+int ft4s_ensure_channel(cwslg_ctx *c, Channel &ch, bool want)
+{
+    SyncChannelBuffers &b = ch.syncbuf;
+    if ((b.d_ft4soft != nullptr) == want) return CWSLG_OK;
+    ch.soft4_t0 = 0;
+    if (!want) { (void)hipFree(b.d_ft4soft); b.d_ft4soft = nullptr; return CWSLG_OK; }
+    HIPCHK(c, hipMalloc((void **)&b.d_ft4soft, (size_t)b.max_cand * 3 * sizeof(Ft4SoftRec)));
+    return CWSLG_OK;
+}
+
 int sync_ensure_channel(cwslg_ctx *c, Channel &ch)
 {
     SyncChannelBuffers &b = ch.syncbuf;
@@ -142,6 +158,7 @@ int sync_ensure_channel(cwslg_ctx *c, Channel &ch)
     if (b.d_block && b.nbins == want_bins && b.max_cand == cfg.max_cand && b.ft4 == ch.sync_ft4 && (b.d_soft != nullptr) == want_soft) return CWSLG_OK;
     sync_free_channel(b);
     ch.soft_t0 = 0;
+    ch.soft4_t0 = 0;
     const size_t sp = ((size_t)(ch.sync_ft4 ? FT4_NHSYM : FT8_NHSYM) * want_bins * sizeof(float) + 255) & ~size_t(255);
     const size_t vec = ((size_t)(FT8_NH1 + 1) * 4 + 255) & ~size_t(255);
     const size_t cand = ((size_t)cfg.max_cand * sizeof(SyncChannelBuffers::Cand) + 255) & ~size_t(255);
@@ -172,6 +189,7 @@ int sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
     const SyncConfig &cfg = c->sync_cfg;
     std::vector<SyncWork> works8, works4;
     std::vector<Ft4Work> works4c;
+    std::vector<Ft4SoftRec *> soft4;                          // cwslg_enable_ft4_softbits: one record array per FT4 channel, in works4c's order
     std::vector<Ft8SoftRec *> soft8;                          // cwslg_enable_ft8_softbits: one record array per FT8 channel, in works8's order
     for (int id : emitted) {
         Channel &ch = c->chans[id];
@@ -199,6 +217,14 @@ int sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
             f.rec = (Ft4Rec *)ch.syncbuf.d_rec; f.nrec = ch.syncbuf.d_nrec; f.cd_dbg = ch.syncbuf.d_cd_dbg;
             works4c.push_back(f);
         }
+        if (ch.sync_ft4) {
+            const bool soft = cfg.ft4_coherent && cfg.ft4_soft;
+            if ((rc = ft4s_ensure_channel(c, ch, soft)) != CWSLG_OK) return rc;
+            if (soft) {
+                soft4.push_back(ch.syncbuf.d_ft4soft);
+                ch.soft4_t0 = ch.frame_t0;                    // the soft-bit records now queued belong to this frame (feature or coherent stage off: the OLD epoch stays, nothing to fetch)
+            }
+        }
     }
     if (works8.empty() && works4.empty()) return CWSLG_OK;
     const size_t n8 = works8.size(), n4 = works4.size();
@@ -219,10 +245,13 @@ int sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
     };
     WorkBuf *wb4 = nullptr;
     if (!works4c.empty()) {
-        wb4 = acquire_workbuf(c, works4c.size() * sizeof(Ft4Work));
+        // (the FT4 soft-bit launch's record pointers ride behind the descriptors, as the FT8 ones do above)
+        const size_t wb4_bytes = works4c.size() * sizeof(Ft4Work) + soft4.size() * sizeof(Ft4SoftRec *);
+        wb4 = acquire_workbuf(c, wb4_bytes);
         if (!wb4) return fail(c, CWSLG_ERR_NOMEM, "work buffer allocation failed");
         std::memcpy(wb4->h, works4c.data(), works4c.size() * sizeof(Ft4Work));
-        HIPCHK(c, upload_workbuf(c, wb4, works4c.size() * sizeof(Ft4Work)));
+        if (!soft4.empty()) std::memcpy((Ft4Work *)wb4->h + works4c.size(), soft4.data(), soft4.size() * sizeof(Ft4SoftRec *));
+        HIPCHK(c, upload_workbuf(c, wb4, wb4_bytes));
     }
     hipEvent_t ea, eb;
     // CWSLG_SYNC_VARIANT bit 3: the candidate kernel on a side stream, overlapping the next demod launch.  Measured and left off:
@@ -361,6 +390,10 @@ int sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
             hipLaunchKernelGGL(ft4_dft567_mfma_kernel, dim3(9, (unsigned)n4), dim3(256), 0, c->stream, f4, c->ft4_tables);
             hipLaunchKernelGGL(ft4_fft64_unpack_kernel, dim3(284, (unsigned)n4), dim3(64), 0, c->stream, f4, c->ft4_tables);
             hipLaunchKernelGGL(ft4_refine_kernel, dim3((unsigned)cfg.max_cand, (unsigned)n4), dim3(256), 0, c->stream, f4, c->ft4_tables, cfg.max_cand);
+            // soft bits: one workgroup per record slot behind the refinement; nrec and the candidate count are read on the device
+            if (!soft4.empty())
+                hipLaunchKernelGGL(ft4_softbits_kernel, dim3(3u * (unsigned)cfg.max_cand, (unsigned)n4), dim3(256), 0, c->stream, f4,
+                                   (Ft4SoftRec *const *)(f4 + works4c.size()), c->ft4_tables, c->sync_shared.ft4_w32, cfg.max_cand);
         }
     }
     if (chain_async) {
@@ -409,6 +442,7 @@ int cwslg_enable_sync(cwslg_ctx *c, int enable, float syncmin, int max_cand, int
         if (cfg.ib < cfg.ia) return fail(c, CWSLG_ERR_ARG, "empty sync frequency range");
         cfg.nbins = (cfg.ib + 13 + 31) / 32 * 32;   // row pitch = whole 128-byte lines (ft8_sync_chan_kernel fetches one line per band and step)
         cfg.ft8_soft = c->sync_cfg.ft8_soft;
+        cfg.ft4_soft = c->sync_cfg.ft4_soft;
         if (cfg.ft8_soft) cfg.nbins = (cfg.ib + 15 + 31) / 32 * 32;   // soft bits on: tone 7 of bin ib (ib + 14) lies inside the row
         hipSetDevice(c->device);
         cfg.ft4_coherent = c->sync_cfg.ft4_coherent;
@@ -566,6 +600,63 @@ int cwslg_fetch_ft4_sync(cwslg_ctx *c, int ch_id, cwslg_ft4_sync *dst, int max, 
     for (int k = 0; k < cnt; ++k)                               // candidate order, then segment order
         for (int q = 0; q < nrec[k] && q < 3; ++q) {
             if (out < max) std::memcpy(&dst[out], &rec[(size_t)k * 3 + q], sizeof(Ft4Rec));
+            ++out;
+        }
+    *n = std::min(out, max);
+    return CWSLG_OK;
+}
+
+// FT4 soft bits (ft4soft_kernels.hpp).  One record per cwslg_ft4_sync record, compacted from the slot layout by the same nrec walk as
+// cwslg_fetch_ft4_sync; handed out only when soft records, sync records, list and frame are of ONE epoch (soft4_t0 == cand_t0 == frame_t0: the
+// launch that sets soft4_t0 runs behind the refinement of the same boundary) -- after a boundary that ran with the feature or the coherent stage
+// off there is nothing to fetch, never an older slot's records under the newer epoch.
+int cwslg_enable_ft4_softbits(cwslg_ctx *c, int enable)
+{
+    if (!c) return CWSLG_ERR_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    if (enable && !c->sync_cfg.enabled) return fail(c, CWSLG_ERR_ARG, "FT4 soft bits need the sync stage (cwslg_enable_sync)");
+    c->sync_cfg.ft4_soft = enable != 0;
+    return CWSLG_OK;
+}
+
+int cwslg_fetch_ft4_softbits(cwslg_ctx *c, int ch_id, cwslg_ft4_soft *dst, int max, int *n, uint64_t *start_epoch)
+{
+    if (!c || !n || (max > 0 && !dst)) return CWSLG_ERR_ARG;
+    *n = 0;
+    const int *cnt_src = nullptr, *nrec_src = nullptr;
+    const Ft4SoftRec *rec_src = nullptr;
+    int lim = 0;
+    ResultFetch rf;
+    {
+        std::lock_guard<std::mutex> g(c->mu);
+        if (ch_id < 0 || ch_id >= (int)c->chans.size() || !c->chans[ch_id].open) return fail(c, CWSLG_ERR_ARG, "bad channel id");
+        Channel &ch = c->chans[ch_id];
+        if (!ch.sync_ft4) return fail(c, CWSLG_ERR_MODE, "FT4 soft bits exist for FT4 channels only (mode %s)", ch.mode.c_str());
+        if (!ch.have_frame || !ch.syncbuf.d_block || !ch.syncbuf.d_ft4c || !ch.syncbuf.d_ft4soft || !ch.soft4_t0 || ch.soft4_t0 != ch.frame_t0 ||
+            ch.soft4_t0 != ch.cand_t0)
+            return CWSLG_ERR_NO_FRAME;
+        hipSetDevice(c->device);
+        if (start_epoch) *start_epoch = ch.soft4_t0;
+        cnt_src = ch.syncbuf.d_ncand; nrec_src = ch.syncbuf.d_nrec; rec_src = ch.syncbuf.d_ft4soft; lim = ch.syncbuf.max_cand;
+        int rc = begin_result_fetch(c, ch, rf);
+        if (rc) return rc;
+    }
+    static_assert(sizeof(cwslg_ft4_soft) == sizeof(Ft4SoftRec), "record layout");
+    int cnt = 0;
+    HIPCHK(c, hipStreamWaitEvent(rf.fs, rf.ev, 0));
+    HIPCHK(c, hipMemcpyAsync(&cnt, cnt_src, sizeof(int), hipMemcpyDeviceToHost, rf.fs));
+    HIPCHK(c, hipStreamSynchronize(rf.fs));
+    cnt = std::max(0, std::min(cnt, lim));
+    if (cnt <= 0) return CWSLG_OK;
+    std::vector<int> nrec((size_t)cnt);
+    std::vector<Ft4SoftRec> rec((size_t)cnt * 3);
+    HIPCHK(c, hipMemcpyAsync(nrec.data(), nrec_src, (size_t)cnt * sizeof(int), hipMemcpyDeviceToHost, rf.fs));
+    HIPCHK(c, hipMemcpyAsync(rec.data(), rec_src, (size_t)cnt * 3 * sizeof(Ft4SoftRec), hipMemcpyDeviceToHost, rf.fs));
+    HIPCHK(c, hipStreamSynchronize(rf.fs));
+    int out = 0;
+    for (int k = 0; k < cnt; ++k)                               // candidate order, then segment order: entry q of cwslg_fetch_ft4_sync
+        for (int q = 0; q < nrec[k] && q < 3; ++q) {
+            if (out < max) std::memcpy(&dst[out], &rec[(size_t)k * 3 + q], sizeof(Ft4SoftRec));
             ++out;
         }
     *n = std::min(out, max);

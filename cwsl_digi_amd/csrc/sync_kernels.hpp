@@ -43,6 +43,7 @@ struct SyncConfig {
     int order = 0;                        // cwslg_set_candidate_order: 0 strongest first (cut at max_cand in that order), 1 ascending frequency (cut in THAT order)
     int f_lo_hz = 200, f_hi_hz = 3000;
     int ia = 64, ib = 960, nbins = 976;   // derived: bin range and stored row length (ib+13 rounded up to 16)
+    bool ft4_soft = false;                // cwslg_enable_ft4_softbits: soft bits per refined FT4 sync record (ft4soft_kernels.hpp)
     bool ft8_soft = false;                // cwslg_enable_ft8_softbits: soft bits per FT8 candidate (ft8soft_kernels.hpp); the row then holds tone 7 of bin ib (ib+15 rounded up)
 };
 
@@ -58,6 +59,7 @@ struct SyncShared {
     SyncTables t4{};                      // FT4 set (w15 -> W_9, w1920 -> W_1152, w3840 -> W_2304)
     float2 *d_ft4c = nullptr;             // FT4 coherent-sync tables (ft4sync_kernels.hpp), one allocation
     float *d_ft4c_win = nullptr;
+    const float2 *ft4_w32 = nullptr;      // inside d_ft4c: [32] (cos, +sin) of 2 pi p / 32, ft4_softbits_kernel's symbol spectra (ft4soft_kernels.hpp)
 };
 
 struct SyncChannelBuffers {
@@ -75,6 +77,7 @@ struct SyncChannelBuffers {
     float2 *d_y = nullptr, *d_cx = nullptr, *d_cd_dbg = nullptr;
     void *d_rec = nullptr;                // Ft4Rec [max_cand][3]
     int *d_nrec = nullptr;                // [max_cand]
+    struct Ft4SoftRec *d_ft4soft = nullptr;   // [max_cand][3], the slot layout of d_rec; an allocation of its own, only while cwslg_enable_ft4_softbits is on
 };
 
 struct alignas(16) SyncWork {
@@ -93,6 +96,7 @@ inline void sync_free_channel(SyncChannelBuffers &b)
 {
     if (b.d_block) (void)hipFree(b.d_block);
     if (b.d_ft4c) (void)hipFree(b.d_ft4c);
+    if (b.d_ft4soft) (void)hipFree(b.d_ft4soft);
     b = SyncChannelBuffers();
 }
 inline void sync_free_shared(SyncShared &s)

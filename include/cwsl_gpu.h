@@ -417,6 +417,52 @@ int cwslg_fetch_ft4_sync(cwslg_ctx *ctx, int ch_id, cwslg_ft4_sync *dst, int max
 typedef struct { float llr[174]; float sigma; int32_t nsync; } cwslg_ft8_soft;   /* 704 bytes */
 int cwslg_enable_ft8_softbits(cwslg_ctx *ctx, int enable);
 int cwslg_fetch_ft8_softbits(cwslg_ctx *ctx, int ch_id, cwslg_ft8_soft *dst, int max, int *n, uint64_t *start_epoch);
+/* FT4 soft bits (row a13; PARITY UNPINNED, restated from upstream ft4_decode's last stage before LDPC: the final ft4_downsample at the corrected
+ * frequency, get_ft4_bitmetrics' three metric sets, the sync-quality counts nsync / nqual, normalizebmet, scalefac = 2.83).  One record per
+ * cwslg_ft4_sync record of the SAME epoch, in the same order -- candidate order, then segment order: record q belongs to entry q of
+ * cwslg_fetch_ft4_sync -- computed on the device from the frame spectrum and the records the refinement has just written.  A consumer (an
+ * in-process LDPC decoder, a pre-filter ahead of jt9, a quality figure per spot) gets this without pulling the int16 frame back and redoing the
+ * 72576-point spectrum, the 4032-point inverse transform at f1 and 103 symbol transforms per record on the host.  Off by default; while it is
+ * off nothing changes (launches, buffers, lists, frames).  Every operation below is one un-fused float32 operation except where an fmaf is written.
+ *   Baseband: cb[0..4031] is exactly what the refinement stage computes for a candidate frequency, evaluated at f1_hz instead of f0_hz:
+ *       i0 = lroundf(f1 / df), the same 630 windowed bins, the same 63 x 64 inverse transform, the same unit-mean-power normalisation over 4032
+ *       samples (oracle/ft4sync_oracle.c:orc_ft4_downsample states it).  Upstream divides by NSS NN = 3296 here instead of 4032: that scales
+ *       sigma only; the llr are scale-free up to rounding.
+ *   Symbols: cd[32 k + t] = cb[ibest + 32 k + t], k = 0..102, t = 0..31; +0 where the index falls outside 0..4031.
+ *   Symbol spectra: cs[k][q], q = 0..3, a 32-term chain in ascending t from z = (+0, +0) with c = cd[32 k + t] and
+ *       w = w32[(q t) mod 32] = (float cos, float sin) of the double angle 2 pi p / 32 (the four cardinal points exact, as in the csync table):
+ *           zr = fmaf(c.r, w.x, zr);  zr = fmaf(c.i, w.y, zr);
+ *           zi = fmaf(c.i, w.x, zi);  zi = fmaf(-c.r, w.y, zi);
+ *       The magnitude of a complex z is |z| = sqrtf(fmaf(z.r, z.r, z.i * z.i)) everywhere below; complex sums add real and imaginary parts.
+ *   nsync (0..16): over the 16 Costas symbols k = 33 b + s (b, s = 0..3) the number whose FIRST maximum over q of |cs[k][q]| (ties to the lowest
+ *       q) is at icos4[b][s]; the blocks are 0132 1023 2310 3201.  Upstream stops at nsync < 8; here every record is delivered and the consumer
+ *       decides.
+ *   Metric sets: three, of 206 entries each.  graymap g = 0,1,3,2; bit ib of a group of nb bits pairs with index bit nb - 1 - ib (most
+ *       significant bit first); a metric is max(s2[i] : index bit set) - max(s2[i] : index bit clear), exact float32 max and subtract.
+ *       Set 0: per symbol k, s2[v] = |cs[k][g[v]]|, v = 0..3 -> bm0[2 k + ib], ib = 0, 1.
+ *       Set 1: pairs ks = 0, 2, ..., 100, i = 0..15: s2[i] = |cs[ks][g[i>>2]] + cs[ks+1][g[i&3]]| -> bm1[2 ks .. 2 ks + 3];
+ *           bm1[204..205] = bm0[204..205].
+ *       Set 2: groups ks = 0, 4, ..., 96, i = 0..255:
+ *           s2[i] = |((cs[ks][g[i>>6]] + cs[ks+1][g[(i>>4)&3]]) + cs[ks+2][g[(i>>2)&3]]) + cs[ks+3][g[i&3]]| -> bm2[2 ks .. 2 ks + 7];
+ *           bm2[200..203] = bm1[200..203], bm2[204..205] = bm0[204..205].
+ *       The copies are taken before normalisation.
+ *   nqual (0..32): hard[t] = (bm0[t] >= 0); the number of agreements with 0,0,0,1,1,0,1,1 at t = 0..7, 0,1,0,0,1,1,1,0 at t = 66..73,
+ *       1,1,1,0,0,1,0,0 at t = 132..139 and 1,0,1,1,0,0,0,1 at t = 198..205 (the gray-decoded Costas blocks).  Upstream requires at least 20.
+ *   Normalisation per set (normalizebmet over all 206 entries), the sums in the order a 64-lane wave evaluates them: pad b to 256 entries with
+ *       +0; a[l] = ((b[l] + b[l+64]) + b[l+128]) + b[l+192], l = 0..63; six halving steps a[l] = a[l] + a[l+h] for l < h, h = 32, 16, 8, 4, 2, 1;
+ *       S1 = a[0]; S2 the same tree over fl(b b); mean = S1 / 206.0f, m2 = S2 / 206.0f, var = m2 - fl(mean mean);
+ *       sigma = sqrtf(var > 0 ? var : m2).
+ *   llr[set][0..57], [58..115], [116..173] come from entries 8..65, 74..131, 140..197 (the data symbols), each fl(fl(b / sigma) 2.83f); every llr
+ *       of a set +0 if its sigma == 0.  llr > 0 means bit 1.  (Upstream's rvec scrambling is a matter of the 77 message bits after decoding, not
+ *       of the metrics.)
+ * cwslg_enable_ft4_softbits needs the sync stage enabled (CWSLG_ERR_ARG otherwise) and applies from the next boundary on; a boundary at which
+ * cwslg_enable_ft4_coherent is off produces no records.  cwslg_fetch_ft4_softbits hands the records out like cwslg_fetch_ft4_sync (same ticket,
+ * *n = min(record count, max)); it returns CWSLG_ERR_MODE for a channel that is not FT4 and CWSLG_ERR_NO_FRAME unless soft records, sync
+ * records, candidate list and frame belong to one epoch -- after a boundary that ran with the feature off there is nothing to fetch, never an
+ * older slot's records under the newer epoch. */
+typedef struct { float llr[3][174]; float sigma[3]; int32_t nsync; int32_t nqual; int32_t pad_; } cwslg_ft4_soft;   /* 2112 bytes */
+int cwslg_enable_ft4_softbits(cwslg_ctx *ctx, int enable);
+int cwslg_fetch_ft4_softbits(cwslg_ctx *ctx, int ch_id, cwslg_ft4_soft *dst, int max, int *n, uint64_t *start_epoch);
 int cwslg_fetch_slot(cwslg_ctx *ctx, int ch_id, int16_t *frame, size_t cap, void *list, size_t list_bytes,
                      cwslg_ft4_sync *ft4, int max_ft4, cwslg_slot_result *out);
 int cwslg_set_ft4_syncmin(cwslg_ctx *ctx, float syncmin);

@@ -56,6 +56,8 @@ public:
     void process() { check(c_, cwslg_process(c_)); }
     // soft bits per FT8 sync candidate from the next boundary on (needs the sync stage: cwslg_enable_sync) -- SsbChannel::fetchFt8Softbits
     void enableFt8Softbits(bool enable = true) { check(c_, cwslg_enable_ft8_softbits(c_, enable ? 1 : 0)); }
+    // soft bits per refined FT4 sync record from the next boundary on (needs the sync stage; records only while the coherent stage runs) -- SsbChannel::fetchFt4Softbits
+    void enableFt4Softbits(bool enable = true) { check(c_, cwslg_enable_ft4_softbits(c_, enable ? 1 : 0)); }
     void synchronize() { check(c_, cwslg_synchronize(c_)); }
     // One block for each of several receivers in ONE call (cwslg_push_iq_many): for a host that serves thousands of streams, where a
     // per-receiver push per block (Receiver.hpp:242-249, ReceiverPort::push below) would mean hundreds of thousands of copies a second.
@@ -181,6 +183,18 @@ public:
         out.resize(max);
         int n = 0;
         const int rc = cwslg_fetch_ft8_softbits(ctx_.raw(), id_, out.data(), max, &n, startEpoch);
+        if (rc == CWSLG_ERR_NO_FRAME) { out.clear(); return 0; }
+        check(ctx_.raw(), rc);
+        out.resize(n);
+        return n;
+    }
+    // FT4 channels with Context::enableFt4Softbits: record q (three sets of 174 bit metrics, their sigma, nsync, nqual) belongs to entry q of
+    // cwslg_fetch_ft4_sync of the same epoch -- cwslg_fetch_ft4_softbits; 0 records while none of the current epoch exist
+    int fetchFt4Softbits(std::vector<cwslg_ft4_soft> &out, int max = 1800, std::uint64_t *startEpoch = nullptr)
+    {
+        out.resize(max);
+        int n = 0;
+        const int rc = cwslg_fetch_ft4_softbits(ctx_.raw(), id_, out.data(), max, &n, startEpoch);
         if (rc == CWSLG_ERR_NO_FRAME) { out.clear(); return 0; }
         check(ctx_.raw(), rc);
         out.resize(n);
