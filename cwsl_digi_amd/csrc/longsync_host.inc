@@ -97,6 +97,9 @@ int long_fst4w_params(const LongConfig &cfg, Fst4wParams *P, int *nband)
     if (inb < ina || inb >= nnw || nnw > F4W_NNW) return CWSLG_ERR_ARG;
     const int jlo = (int)std::lround((float)ina * df2 / df1) - ndh, jhi = (int)std::lround((float)inb * df2 / df1) + ndh;
     if (jlo < 0 || jhi > F4W_NMAX / 2 || jhi - jlo + 1 > F4W_M || inb - ina + 9 > 1024) return CWSLG_ERR_ARG;
+    // what the band kernel's table holds: F4W_TP entries per residue mod 125, and dlo(c) computed for jlo > 125 (the 100 Hz clamp keeps
+    // jlo at 11986 and above, so only the first limit is reachable: 1400..1607 is the widest window above 1400 Hz, nband 24936)
+    if ((jhi - jlo + 1 + 124) / 125 > F4W_TP || jlo <= 125) return CWSLG_ERR_ARG;
     P->ina = ina; P->inb = inb; P->ia = ia; P->ib = ib; P->ndh = ndh; P->jlo = jlo; P->nnw = nnw;
     P->df1 = df1; P->df2 = df2; P->minsync = cfg.minsync;
     *nband = jhi - jlo + 1;
@@ -110,6 +113,7 @@ int long_ensure_fst4w_tables(cwslg_ctx *c)
     if (rc) return rc;
     Fst4wParams P; int nband = 0;
     if ((rc = long_fst4w_params(c->long_cfg, &P, &nband)) != CWSLG_OK) return fail(c, rc, "FST4W search window out of range");
+    if ((nband + 124) / 125 > F4W_TP || P.jlo <= 125) return fail(c, CWSLG_ERR_ARG, "FST4W search window out of range");   // guard: long_fst4w_params rejects these
     if (s.d_f4w_T && s.f4w_jlo == P.jlo && s.f4w_nband == nband) return CWSLG_OK;
     if (s.d_f4w_T) { HIPCHK(c, sync_streams(c)); (void)hipFree(s.d_f4w_T); s.d_f4w_T = nullptr; }
     constexpr double pi = 3.14159265358979323846;
@@ -127,7 +131,6 @@ int long_ensure_fst4w_tables(cwslg_ctx *c)
             }
         }
     }
-    if ((nband + 124) / 125 > F4W_TP || P.jlo <= 125) return fail(c, CWSLG_ERR_ARG, "FST4W search window out of range");
     if ((rc = long_upload(c, T, &s.d_f4w_T)) != CWSLG_OK) return rc;
     s.f4w_jlo = P.jlo; s.f4w_nband = nband;
     return CWSLG_OK;

@@ -710,9 +710,10 @@ __global__ __launch_bounds__(512) void fst4w_cand_kernel(const LongWork *__restr
     const float base = s_base;
     for (int l = tid; l < width; l += 512) s_s2[l] = s_s2[l] / base;
     __syncthreads();
+    const float outside = 0.0f / base;                   // s2 = s2 / base runs over the whole array: 0 outside the window, NaN when base is 0
     for (int i = tid; i < P.nnw; i += 512) {             // the normalised comb spectrum, for the parity tests
         const int l = i - lo;
-        as_global_rw(w->vec)[i] = (l >= 0 && l < width) ? s_s2[l] : 0.0f;
+        as_global_rw(w->vec)[i] = (l >= 0 && l < width) ? s_s2[l] : outside;
     }
     int ia = P.ia, ib = P.ib;
     if (ia < 3) ia = 3;
@@ -723,8 +724,9 @@ __global__ __launch_bounds__(512) void fst4w_cand_kernel(const LongWork *__restr
     while (ncand < F4W_MAXCAND) {
         unsigned long long best = 0ull;
         for (int i = ia + tid; i <= ib; i += 512) {
-            unsigned u = __float_as_uint(s_s2[i - lo]);
-            u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+            const float v = s_s2[i - lo];
+            unsigned u = __float_as_uint(v);
+            u = (v != v) ? 0u : ((u & 0x80000000u) ? ~u : (u | 0x80000000u));                             // a NaN orders below every number (-inf is 0x007FFFFF)
             const unsigned long long key = ((unsigned long long)u << 32) | (unsigned)(0xFFFFFF - i);      // maxloc: first maximum
             best = key > best ? key : best;
         }
@@ -736,7 +738,11 @@ __global__ __launch_bounds__(512) void fst4w_cand_kernel(const LongWork *__restr
         }
         const unsigned long long key = s_key[0];
         __syncthreads();
-        const int ip = 0xFFFFFF - (int)(key & 0xFFFFFFu);
+        // The restatement scans from ia and replaces its pick on `>`: a NaN elsewhere never replaces a number, and a NaN AT ia is never
+        // replaced.  (An all-zero frame has base = 0 and s2 = 0/0 over the whole window: one record (ia, NaN), whose clean-up writes zeros,
+        // and the next pass stops on 0 < minsync.  Ordered by the raw bit pattern a positive NaN was the maximum a hundred times over.)
+        int ip = 0xFFFFFF - (int)(key & 0xFFFFFFu);
+        if (s_s2[ia - lo] != s_s2[ia - lo]) ip = ia;
         const float pval = s_s2[ip - lo];
         if (pval < P.minsync) break;
         if (tid < 7) {

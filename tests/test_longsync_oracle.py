@@ -63,8 +63,18 @@ def test_wspr_search_finds_the_transmissions(oracle, wspr_frame):
 
 def test_wspr_noise_only_has_no_strong_sync(oracle):
     rng = np.random.default_rng(3)
-    cands = oracle.wspr_search(to_i16(rng.standard_normal(N) * 300))
-    assert all(c[3] < 0.25 for c in cands)
+    a = rng.standard_normal(N) * 300
+    cands, arr = oracle.wspr_search(to_i16(a), want_arrays=True)
+    sm = arr["smspec"]
+    floor = np.float32(0.1 * float(np.float32(10.0 ** -0.8)))
+    # stationary noise barely reaches wsprd's -8 dB threshold: 8 of the 411 bins lie above the floor value, three of them peaks inside +-110 Hz
+    assert sm.min() == floor and (sm > floor).sum() == 8 and 0.158 < sm.max() < 0.21
+    assert len(cands) == 3 and 0.05 < max(c[3] for c in cands) < 0.25
+    # the same noise in the first 30 s only (what a short slot leaves in the frame): ten candidates, none with a strong sync
+    b = a.copy()
+    b[360000:] = 0
+    cands = oracle.wspr_search(to_i16(b))
+    assert len(cands) == 10 and 0.15 < max(c[3] for c in cands) < 0.25
 
 
 def test_fst4w_band_and_candidates(oracle):
@@ -87,4 +97,7 @@ def test_fst4w_band_and_candidates(oracle):
     assert len(cands) <= 100 and all(c[1] >= 1.2 for c in cands)
     s2 = arr["s2"]
     assert (s2[:ina] == 0).all() and s2[ina + 3:inb - 2].min() > 0
-    assert oracle.fst4w_candidates(to_i16(rng.standard_normal(N) * 300))[:1] == [] or True      # noise: few or none above 1.2
+    noise = to_i16(rng.standard_normal(N) * 300)                   # noise: none above 1.2 (the strongest bin is 1.193), 56 above 0.8
+    assert oracle.fst4w_candidates(noise) == []
+    low = oracle.fst4w_candidates(noise, minsync=0.8)
+    assert len(low) == 56 and 1.15 < low[0][1] < 1.2 and all(c[1] >= 0.8 for c in low)
