@@ -94,6 +94,14 @@ class Ft8Soft(C.Structure):
     _fields_ = [("llr", C.c_float * 174), ("sigma", C.c_float), ("nsync", C.c_int32)]
 
 
+class Ft8Msg(C.Structure):
+    _fields_ = [("bits", C.c_uint8 * 12), ("iters", C.c_int16), ("nbad", C.c_int16), ("nharderr", C.c_int16), ("crc_ok", C.c_uint8), ("pad_", C.c_uint8)]
+
+
+# numpy view of cwslg_ft8_msg (20 bytes)
+FT8_MSG_DTYPE = np.dtype([("bits", np.uint8, 12), ("iters", np.int16), ("nbad", np.int16), ("nharderr", np.int16), ("crc_ok", np.uint8), ("pad_", np.uint8)])
+
+
 class Ft4Soft(C.Structure):
     _fields_ = [("llr", (C.c_float * 174) * 3), ("sigma", C.c_float * 3), ("nsync", C.c_int32), ("nqual", C.c_int32), ("pad_", C.c_int32)]
 
@@ -139,6 +147,7 @@ ABI_SYMBOLS = [
     "cwslg_synchronize", "cwslg_fetch_frame", "cwslg_fetch_slot", "cwslg_write_wav", "cwslg_fetch_audio_f32", "cwslg_frame_device_ptrs",
     "cwslg_enable_sync", "cwslg_set_candidate_order", "cwslg_fetch_candidates", "cwslg_set_ft4_syncmin", "cwslg_enable_ft4_coherent", "cwslg_fetch_ft4_sync",
     "cwslg_enable_ft8_softbits", "cwslg_fetch_ft8_softbits", "cwslg_enable_ft4_softbits", "cwslg_fetch_ft4_softbits", "cwslg_sync_debug_fetch", "cwslg_get_stats", "cwslg_reset_stats",
+    "cwslg_set_ldpc_code", "cwslg_enable_ft8_decode", "cwslg_fetch_ft8_decode", "cwslg_ldpc_decode",
     "cwslg_set_timing", "cwslg_demod_kernel_name", "cwslg_stream", "cwslg_channel_constants", "cwslg_phasor_checkpoint_stride", "cwslg_channel_phasor_checkpoints",
     "cwslg_slot_clock_next", "cwslg_pool_sizing", "cwslg_find_band", "cwslg_parse_decode_line",
     "cwslg_decoder_block_bytes", "cwslg_decoder_block_field", "cwslg_fill_decoder_block", "cwslg_decoder_route", "cwslg_decoder_command",
@@ -226,6 +235,10 @@ def load_library(build_if_missing=True):
     L.cwslg_fetch_ft4_sync.argtypes = [vp, i32, C.POINTER(Ft4Sync), i32, C.POINTER(i32), C.POINTER(u64)]
     L.cwslg_enable_ft8_softbits.argtypes = [vp, i32]
     L.cwslg_fetch_ft8_softbits.argtypes = [vp, i32, C.POINTER(Ft8Soft), i32, C.POINTER(i32), C.POINTER(u64)]
+    L.cwslg_set_ldpc_code.argtypes = [vp, vp]
+    L.cwslg_enable_ft8_decode.argtypes = [vp, i32, i32, i32]
+    L.cwslg_fetch_ft8_decode.argtypes = [vp, i32, C.POINTER(Ft8Msg), i32, C.POINTER(i32), C.POINTER(u64)]
+    L.cwslg_ldpc_decode.argtypes = [vp, vp, i32, i32, vp]
     L.cwslg_enable_ft4_softbits.argtypes = [vp, i32]
     L.cwslg_fetch_ft4_softbits.argtypes = [vp, i32, C.POINTER(Ft4Soft), i32, C.POINTER(i32), C.POINTER(u64)]
     L.cwslg_sync_debug_fetch.argtypes = [vp, i32, i32, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(i32)]
@@ -612,6 +625,39 @@ class Context:
         rec = buf[:n.value]
         out = (np.ascontiguousarray(rec[:, :174]), rec[:, 174].copy(), rec[:, 175].copy().view(np.int32))
         return out + (t0.value,) if with_epoch else out
+
+    def set_ldpc_code(self, nm):
+        """Load the (174, 91) parity-check table: nm uint8[83, 7], 1-based codeword positions, a row of weight 6 ends in one 0 (the integrator's own
+        copy of WSJT-X's Nm).  Raises ERR_ARG for a table that fails validation; the code loaded before stays."""
+        nm = np.ascontiguousarray(nm, dtype=np.uint8)
+        if nm.size != 83 * 7:
+            raise CwslGpuError(-6, "the parity-check table is 83 x 7")
+        self._chk(self.L.cwslg_set_ldpc_code(self.h, nm.ctypes.data))
+
+    def enable_ft8_decode(self, enable=True, max_iter=30, min_nsync=7):
+        """LDPC decode + CRC-14 per FT8 sync candidate (cwslg_ft8_msg); needs a loaded code, enable_sync and enable_ft8_softbits; applies from the
+        next boundary on."""
+        self._chk(self.L.cwslg_enable_ft8_decode(self.h, int(enable), int(max_iter), int(min_nsync)))
+
+    def fetch_ft8_decode(self, ch, max_cand=600, with_epoch=False):
+        """-> None unless decode records of the channel's current epoch exist, else a numpy record array (FT8_MSG_DTYPE: bits uint8[12], iters, nbad,
+        nharderr, crc_ok) whose row q belongs to entry q of fetch_candidates' list of the same epoch (with_epoch: (records, frame start epoch))."""
+        buf = np.zeros(max(int(max_cand), 1), FT8_MSG_DTYPE)
+        n = C.c_int()
+        t0 = C.c_uint64()
+        rc = self.L.cwslg_fetch_ft8_decode(self.h, ch, buf.ctypes.data_as(C.POINTER(Ft8Msg)), int(max_cand), C.byref(n), C.byref(t0))
+        if rc == ERR_NO_FRAME:
+            return None
+        self._chk(rc)
+        rec = buf[:n.value].copy()
+        return (rec, t0.value) if with_epoch else rec
+
+    def ldpc_decode(self, llr, max_iter=30):
+        """The decode kernel on caller-supplied metrics, llr float32[n, 174] (n >= 0), no nsync filter; synchronous.  -> record array [n]."""
+        llr = np.ascontiguousarray(llr, dtype=np.float32).reshape(-1, 174)
+        out = np.zeros(len(llr), FT8_MSG_DTYPE)
+        self._chk(self.L.cwslg_ldpc_decode(self.h, llr.ctypes.data if len(llr) else None, len(llr), int(max_iter), out.ctypes.data if len(llr) else None))
+        return out
 
     def enable_ft4_softbits(self, enable=True):
         """Soft bits per refined FT4 sync record (cwslg_ft4_soft); needs enable_sync; applies from the next boundary on."""

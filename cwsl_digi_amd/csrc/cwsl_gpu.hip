@@ -47,6 +47,7 @@
 #include "sync_kernels.hpp"
 #include "ft4sync_kernels.hpp"
 #include "ft8soft_kernels.hpp"
+#include "ldpc_kernels.hpp"
 #include "ft4soft_kernels.hpp"
 #include "longsync_kernels.hpp"
 
@@ -203,6 +204,7 @@ struct Channel {
     uint64_t cand_t0 = 0;              // start epoch of the frame the candidate lists on the device were computed from (0: none yet)
     uint64_t soft_t0 = 0;              // ... the FT8 soft-bit records were computed from (cwslg_enable_ft8_softbits; 0: none)
     uint64_t soft4_t0 = 0;             // ... the FT4 soft-bit records were computed from (cwslg_enable_ft4_softbits; 0: none)
+    uint64_t msg_t0 = 0;               // ... the FT8 decode records were computed from (cwslg_enable_ft8_decode; 0: none)
     SyncChannelBuffers syncbuf;
 };
 
@@ -529,9 +531,9 @@ int launch_phasor_jobs(cwslg_ctx *c, const std::vector<PhasorJob> &jobs)
     const int n = (int)jobs.size();
     unsigned max_ckpt = 0;
     for (const PhasorJob &j : jobs) max_ckpt = std::max(max_ckpt, j.n_ckpt);
-    hipLaunchKernelGGL(phasor_coarse_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, (const PhasorJob *)w->d, n);
+    hipLaunchKernelGGL(phasor_table_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream, (const PhasorJob *)w->d, n, 0);
     const unsigned segs = (max_ckpt + kCoarse - 1) / kCoarse;
-    hipLaunchKernelGGL(phasor_fine_kernel, dim3((segs + 63) / 64, (unsigned)n), dim3(64), 0, c->stream, (const PhasorJob *)w->d);
+    hipLaunchKernelGGL(phasor_table_kernel, dim3((segs + 63) / 64, (unsigned)n), dim3(64), 0, c->stream, (const PhasorJob *)w->d, n, 1);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(w->done, c->stream));
     w->in_flight = true;

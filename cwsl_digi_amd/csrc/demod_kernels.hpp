@@ -180,21 +180,22 @@ __device__ __forceinline__ v2f cmul_exact_pk(v2f a, v2f b)
 // the same order, so the table is bit-identical to a single serial walk (tests/test_gpu_demod.py).
 constexpr int kCoarse = 256;            // fine checkpoints per coarse segment (= 1024 blocks)
 
-__global__ void phasor_coarse_kernel(const PhasorJob *__restrict__ jobs, int n_jobs)
+// One job -- building the table -- in one kernel, launched once per pass: fine = 0 the coarse walk, grid (ceil(n_jobs / 64)), lane = job;
+// fine = 1 the fill, grid (ceil(max segments / 64), n_jobs), 64 threads: lane = coarse segment, blockIdx.y = job.
+__global__ void phasor_table_kernel(const PhasorJob *__restrict__ jobs, int n_jobs, int fine)
 {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n_jobs) return;
-    const PhasorJob job = jobs[j];
-    float2 p = job.start;                               // (1, 0): SSBD.hpp:121
-    for (unsigned c = 0; c < job.n_ckpt; c += kCoarse) {
-        gst2(job.ckpt + c, p);
-        for (int s = 0; s < kCoarse * kCk; ++s) p = cmul_exact(p, job.inc);
+    if (!fine) {
+        const int j = blockIdx.x * blockDim.x + threadIdx.x;
+        if (j >= n_jobs) return;
+        const PhasorJob job = jobs[j];
+        float2 p = job.start;                           // (1, 0): SSBD.hpp:121
+        for (unsigned c = 0; c < job.n_ckpt; c += kCoarse) {
+            gst2(job.ckpt + c, p);
+            for (int s = 0; s < kCoarse * kCk; ++s) p = cmul_exact(p, job.inc);
+        }
+        return;
     }
-}
-
-// grid (ceil(max segments / 64), n_jobs), 64 threads: lane = coarse segment
-__global__ void phasor_fine_kernel(const PhasorJob *__restrict__ jobs)
-{
+    if ((int)blockIdx.y >= n_jobs) return;
     const PhasorJob job = jobs[blockIdx.y];
     const unsigned seg = blockIdx.x * blockDim.x + threadIdx.x;
     const unsigned c0 = seg * kCoarse;

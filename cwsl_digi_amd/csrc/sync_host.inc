@@ -155,15 +155,20 @@ int sync_ensure_channel(cwslg_ctx *c, Channel &ch)
     const SyncConfig &cfg = c->sync_cfg;
     const int want_bins = ch.sync_ft4 ? FT4_ROW : cfg.nbins;
     const bool want_soft = cfg.ft8_soft && ch.sync_ft8;      // the soft-bit records exist only while the feature is on (a later enable reallocates)
-    if (b.d_block && b.nbins == want_bins && b.max_cand == cfg.max_cand && b.ft4 == ch.sync_ft4 && (b.d_soft != nullptr) == want_soft) return CWSLG_OK;
+    const bool want_msg = want_soft && cfg.ft8_decode;       // ... and so do the decode records
+    if (b.d_block && b.nbins == want_bins && b.max_cand == cfg.max_cand && b.ft4 == ch.sync_ft4 && (b.d_soft != nullptr) == want_soft &&
+        (b.d_msg != nullptr) == want_msg)
+        return CWSLG_OK;
     sync_free_channel(b);
     ch.soft_t0 = 0;
+    ch.msg_t0 = 0;
     ch.soft4_t0 = 0;
     const size_t sp = ((size_t)(ch.sync_ft4 ? FT4_NHSYM : FT8_NHSYM) * want_bins * sizeof(float) + 255) & ~size_t(255);
     const size_t vec = ((size_t)(FT8_NH1 + 1) * 4 + 255) & ~size_t(255);
     const size_t cand = ((size_t)cfg.max_cand * sizeof(SyncChannelBuffers::Cand) + 255) & ~size_t(255);
     const size_t soft = want_soft ? (size_t)cfg.max_cand * sizeof(Ft8SoftRec) : 0;
-    HIPCHK(c, hipMalloc((void **)&b.d_block, sp + 4 * vec + cand + 256 + soft));
+    const size_t msg = want_msg ? (size_t)cfg.max_cand * sizeof(Ft8MsgRec) : 0;
+    HIPCHK(c, hipMalloc((void **)&b.d_block, sp + 4 * vec + cand + 256 + soft + msg));
     char *p = b.d_block;
     b.d_spectra = (float *)p; p += sp;
     b.d_red = (float *)p; p += vec;
@@ -172,7 +177,8 @@ int sync_ensure_channel(cwslg_ctx *c, Channel &ch)
     b.d_jpeak2 = (int *)p; p += vec;
     b.d_cand = (SyncChannelBuffers::Cand *)p; p += cand;
     b.d_ncand = (int *)p; p += 256;
-    if (want_soft) b.d_soft = (Ft8SoftRec *)p;
+    if (want_soft) { b.d_soft = (Ft8SoftRec *)p; p += soft; }
+    if (want_msg) b.d_msg = (Ft8MsgRec *)p;
     b.nbins = want_bins;
     b.max_cand = cfg.max_cand;
     b.ft4 = ch.sync_ft4;
@@ -191,6 +197,7 @@ int sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
     std::vector<Ft4Work> works4c;
     std::vector<Ft4SoftRec *> soft4;                          // cwslg_enable_ft4_softbits: one record array per FT4 channel, in works4c's order
     std::vector<Ft8SoftRec *> soft8;                          // cwslg_enable_ft8_softbits: one record array per FT8 channel, in works8's order
+    std::vector<Ft8MsgRec *> msg8;                            // cwslg_enable_ft8_decode (with soft bits on): one record array per FT8 channel, in works8's order
     for (int id : emitted) {
         Channel &ch = c->chans[id];
         if (!ch.sync_ft8 && !ch.sync_ft4) continue;
@@ -208,6 +215,10 @@ int sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
         if (ch.sync_ft8 && cfg.ft8_soft) {
             soft8.push_back(ch.syncbuf.d_soft);
             ch.soft_t0 = ch.frame_t0;                         // ... and so do the soft-bit records (a boundary with the feature off leaves the OLD epoch: nothing to fetch)
+            if (cfg.ft8_decode) {
+                msg8.push_back(ch.syncbuf.d_msg);
+                ch.msg_t0 = ch.frame_t0;                      // ... and the decode records, under the same rule
+            }
         }
         if (ch.sync_ft4 && cfg.ft4_coherent) {
             if ((rc = ft4c_ensure_tables(c)) != CWSLG_OK || (rc = ft4c_ensure_channel(c, ch)) != CWSLG_OK) return rc;
@@ -229,12 +240,13 @@ int sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
     if (works8.empty() && works4.empty()) return CWSLG_OK;
     const size_t n8 = works8.size(), n4 = works4.size();
     // the soft-bit launch's record pointers ride behind the descriptors in the same buffer (nothing is added while the feature is off)
-    const size_t wb_bytes = (n8 + n4) * sizeof(SyncWork) + soft8.size() * sizeof(Ft8SoftRec *);
+    const size_t wb_bytes = (n8 + n4) * sizeof(SyncWork) + soft8.size() * sizeof(Ft8SoftRec *) + msg8.size() * sizeof(Ft8MsgRec *);
     WorkBuf *wb = acquire_workbuf(c, wb_bytes);
     if (!wb) return fail(c, CWSLG_ERR_NOMEM, "work buffer allocation failed");
     if (n8) std::memcpy(wb->h, works8.data(), n8 * sizeof(SyncWork));
     if (n4) std::memcpy((SyncWork *)wb->h + n8, works4.data(), n4 * sizeof(SyncWork));
     if (!soft8.empty()) std::memcpy((SyncWork *)wb->h + n8 + n4, soft8.data(), soft8.size() * sizeof(Ft8SoftRec *));
+    if (!msg8.empty()) std::memcpy((Ft8SoftRec **)((SyncWork *)wb->h + n8 + n4) + soft8.size(), msg8.data(), msg8.size() * sizeof(Ft8MsgRec *));
     HIPCHK(c, upload_workbuf(c, wb, wb_bytes));
     // one wave per candidate behind whichever search form wrote d_cand / d_ncand (the count is read on the device); its time is part of the
     // stage's span (stats.sync_ms), not of the search's own
@@ -242,6 +254,13 @@ int sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
         if (soft8.empty()) return;
         hipLaunchKernelGGL(ft8_softbits_kernel, dim3((unsigned)((cfg.max_cand + FT8S_WAVES - 1) / FT8S_WAVES), (unsigned)n8), dim3(64 * FT8S_WAVES), 0, st,
                            (const SyncWork *)wb->d, (Ft8SoftRec *const *)((const SyncWork *)wb->d + n8 + n4), cfg.nbins, cfg.max_cand);
+        // the decode: one wave per candidate behind the metrics it reads (same grid, same device-side count); counted as a launch of its own
+        if (msg8.empty()) return;
+        Ft8SoftRec *const *dsoft = (Ft8SoftRec *const *)((const SyncWork *)wb->d + n8 + n4);
+        hipLaunchKernelGGL(ldpc_decode_kernel, dim3((unsigned)((cfg.max_cand + LDPC_WAVES - 1) / LDPC_WAVES), (unsigned)n8), dim3(64 * LDPC_WAVES), 0, st,
+                           (const SyncWork *)wb->d, dsoft, (Ft8MsgRec *const *)(dsoft + n8), (const float *)nullptr, (Ft8MsgRec *)nullptr, 0, cfg.max_cand,
+                           cfg.ldpc_max_iter, cfg.ldpc_min_nsync, (const LdpcTables *)c->sync_shared.d_ldpc);
+        c->stats.sync_launches++;
     };
     WorkBuf *wb4 = nullptr;
     if (!works4c.empty()) {
@@ -443,6 +462,7 @@ int cwslg_enable_sync(cwslg_ctx *c, int enable, float syncmin, int max_cand, int
         cfg.nbins = (cfg.ib + 13 + 31) / 32 * 32;   // row pitch = whole 128-byte lines (ft8_sync_chan_kernel fetches one line per band and step)
         cfg.ft8_soft = c->sync_cfg.ft8_soft;
         cfg.ft4_soft = c->sync_cfg.ft4_soft;
+        cfg.ft8_decode = c->sync_cfg.ft8_decode; cfg.ldpc_max_iter = c->sync_cfg.ldpc_max_iter; cfg.ldpc_min_nsync = c->sync_cfg.ldpc_min_nsync;
         if (cfg.ft8_soft) cfg.nbins = (cfg.ib + 15 + 31) / 32 * 32;   // soft bits on: tone 7 of bin ib (ib + 14) lies inside the row
         hipSetDevice(c->device);
         cfg.ft4_coherent = c->sync_cfg.ft4_coherent;
@@ -554,6 +574,103 @@ int cwslg_fetch_ft8_softbits(cwslg_ctx *c, int ch_id, cwslg_ft8_soft *dst, int m
     cnt = std::max(0, std::min(cnt, lim));
     if (cnt > 0) std::memcpy(dst, tmp.data(), (size_t)cnt * sizeof(Ft8SoftRec));
     *n = cnt;
+    return CWSLG_OK;
+}
+
+// FT8 decode (ldpc_kernels.hpp).  The parity-check table is the caller's data: validated and turned into the kernel's tables on the host
+// (ldpc_host.hpp), uploaded with the context's streams drained -- a new table applies to every launch queued after the call.
+int cwslg_set_ldpc_code(cwslg_ctx *c, const uint8_t *nm)
+{
+    if (!c || !nm) return CWSLG_ERR_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    LdpcTables t;
+    const int why = ldpc_derive(nm, &t);
+    if (why) {
+        static const char *const reason[] = {"", "a position above 174", "a zero that is not the last entry of its row", "a position twice in one row",
+                                             "a position that does not occur exactly three times"};
+        return fail(c, CWSLG_ERR_ARG, "LDPC table rejected: %s", reason[why]);
+    }
+    hipSetDevice(c->device);
+    if (!c->sync_shared.d_ldpc) HIPCHK(c, hipMalloc(&c->sync_shared.d_ldpc, sizeof(LdpcTables)));
+    HIPCHK(c, sync_streams(c));                                // no queued decode launch may still read the old tables
+    HIPCHK(c, hipMemcpy(c->sync_shared.d_ldpc, &t, sizeof(LdpcTables), hipMemcpyHostToDevice));
+    c->sync_shared.ldpc_loaded = true;
+    return CWSLG_OK;
+}
+
+int cwslg_enable_ft8_decode(cwslg_ctx *c, int enable, int max_iter, int min_nsync)
+{
+    if (!c) return CWSLG_ERR_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    SyncConfig &cfg = c->sync_cfg;
+    if (!enable) { cfg.ft8_decode = false; return CWSLG_OK; }
+    if (max_iter < 1 || max_iter > 200 || min_nsync < 0 || min_nsync > 22) return fail(c, CWSLG_ERR_ARG, "FT8 decode parameters out of range");
+    if (!c->sync_shared.ldpc_loaded) return fail(c, CWSLG_ERR_ARG, "FT8 decode needs a parity-check table (cwslg_set_ldpc_code)");
+    if (!cfg.enabled || !cfg.ft8_soft) return fail(c, CWSLG_ERR_ARG, "FT8 decode needs the sync stage and FT8 soft bits (cwslg_enable_sync, cwslg_enable_ft8_softbits)");
+    cfg.ft8_decode = true; cfg.ldpc_max_iter = max_iter; cfg.ldpc_min_nsync = min_nsync;
+    return CWSLG_OK;
+}
+
+// Handed out like the soft-bit records, and only together with them: decode records, soft-bit records, list and frame of ONE epoch.
+int cwslg_fetch_ft8_decode(cwslg_ctx *c, int ch_id, cwslg_ft8_msg *dst, int max, int *n, uint64_t *start_epoch)
+{
+    if (!c || !n || (max > 0 && !dst)) return CWSLG_ERR_ARG;
+    *n = 0;
+    const Ft8MsgRec *src = nullptr;
+    const int *cnt_src = nullptr;
+    int lim = 0;
+    ResultFetch rf;
+    {
+        std::lock_guard<std::mutex> g(c->mu);
+        if (ch_id < 0 || ch_id >= (int)c->chans.size() || !c->chans[ch_id].open) return fail(c, CWSLG_ERR_ARG, "bad channel id");
+        Channel &ch = c->chans[ch_id];
+        if (!ch.sync_ft8) return fail(c, CWSLG_ERR_MODE, "decode records exist for FT8 channels only (mode %s)", ch.mode.c_str());
+        if (!ch.have_frame || !ch.syncbuf.d_block || !ch.syncbuf.d_msg || !ch.msg_t0 || ch.msg_t0 != ch.frame_t0 || ch.msg_t0 != ch.cand_t0 ||
+            ch.msg_t0 != ch.soft_t0)
+            return CWSLG_ERR_NO_FRAME;
+        hipSetDevice(c->device);
+        if (start_epoch) *start_epoch = ch.msg_t0;
+        src = ch.syncbuf.d_msg; cnt_src = ch.syncbuf.d_ncand; lim = std::min(std::max(max, 0), ch.syncbuf.max_cand);
+        int rc = begin_result_fetch(c, ch, rf);
+        if (rc) return rc;
+    }
+    static_assert(sizeof(cwslg_ft8_msg) == sizeof(Ft8MsgRec), "record layout");
+    int cnt = 0;
+    std::vector<Ft8MsgRec> tmp((size_t)lim);
+    HIPCHK(c, hipStreamWaitEvent(rf.fs, rf.ev, 0));
+    HIPCHK(c, hipMemcpyAsync(&cnt, cnt_src, sizeof(int), hipMemcpyDeviceToHost, rf.fs));
+    if (lim > 0) HIPCHK(c, hipMemcpyAsync(tmp.data(), src, (size_t)lim * sizeof(Ft8MsgRec), hipMemcpyDeviceToHost, rf.fs));
+    HIPCHK(c, hipStreamSynchronize(rf.fs));
+    cnt = std::max(0, std::min(cnt, lim));
+    if (cnt > 0) std::memcpy(dst, tmp.data(), (size_t)cnt * sizeof(Ft8MsgRec));
+    *n = cnt;
+    return CWSLG_OK;
+}
+
+// The same kernel on n sets of 174 metrics from host memory, no nsync filter; synchronous (temporary device buffers, the context's stream).
+int cwslg_ldpc_decode(cwslg_ctx *c, const float *llr, int n, int max_iter, cwslg_ft8_msg *out)
+{
+    if (!c || n < 0 || (n > 0 && (!llr || !out))) return CWSLG_ERR_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    if (max_iter < 1 || max_iter > 200) return fail(c, CWSLG_ERR_ARG, "max_iter out of range (1..200)");
+    if (!c->sync_shared.ldpc_loaded) return fail(c, CWSLG_ERR_ARG, "no parity-check table loaded (cwslg_set_ldpc_code)");
+    if (n == 0) return CWSLG_OK;
+    hipSetDevice(c->device);
+    const size_t in_bytes = (size_t)n * LDPC_N * sizeof(float), out_bytes = (size_t)n * sizeof(Ft8MsgRec);
+    char *d = nullptr;
+    HIPCHK(c, hipMalloc((void **)&d, in_bytes + out_bytes));      // (in_bytes is a multiple of 8: the records behind it are aligned)
+    hipError_t e = hipMemcpyAsync(d, llr, in_bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(ldpc_decode_kernel, dim3((unsigned)((n + LDPC_WAVES - 1) / LDPC_WAVES), 1), dim3(64 * LDPC_WAVES), 0, c->stream,
+                           (const SyncWork *)nullptr, (Ft8SoftRec *const *)nullptr, (Ft8MsgRec *const *)nullptr, (const float *)d,
+                           (Ft8MsgRec *)(d + in_bytes), n, 0, max_iter, 0, (const LdpcTables *)c->sync_shared.d_ldpc);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d + in_bytes, out_bytes, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    (void)hipFree(d);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(c, CWSLG_ERR_HIP, "cwslg_ldpc_decode failed: %s", hipGetErrorString(e));
     return CWSLG_OK;
 }
 

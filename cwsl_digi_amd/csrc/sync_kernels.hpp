@@ -45,6 +45,8 @@ struct SyncConfig {
     int ia = 64, ib = 960, nbins = 976;   // derived: bin range and stored row length (ib+13 rounded up to 16)
     bool ft4_soft = false;                // cwslg_enable_ft4_softbits: soft bits per refined FT4 sync record (ft4soft_kernels.hpp)
     bool ft8_soft = false;                // cwslg_enable_ft8_softbits: soft bits per FT8 candidate (ft8soft_kernels.hpp); the row then holds tone 7 of bin ib (ib+15 rounded up)
+    bool ft8_decode = false;              // cwslg_enable_ft8_decode: LDPC(174,91) decode + CRC-14 per FT8 candidate (ldpc_kernels.hpp); runs only while ft8_soft is on too
+    int ldpc_max_iter = 30, ldpc_min_nsync = 7;
 };
 
 struct SyncTables {                       // device pointers: W_NZ, W_128, 0.5 W_2NZ twiddles, optional window
@@ -60,6 +62,8 @@ struct SyncShared {
     float2 *d_ft4c = nullptr;             // FT4 coherent-sync tables (ft4sync_kernels.hpp), one allocation
     float *d_ft4c_win = nullptr;
     const float2 *ft4_w32 = nullptr;      // inside d_ft4c: [32] (cos, +sin) of 2 pi p / 32, ft4_softbits_kernel's symbol spectra (ft4soft_kernels.hpp)
+    void *d_ldpc = nullptr;               // LdpcTables (ldpc_host.hpp) derived from the caller's parity-check table; allocated by the first cwslg_set_ldpc_code
+    bool ldpc_loaded = false;
 };
 
 struct SyncChannelBuffers {
@@ -70,6 +74,7 @@ struct SyncChannelBuffers {
     struct Cand { int freq_bin, time_step; float sync, freq_hz, dt_s; } *d_cand = nullptr;   // [max_cand]
     int *d_ncand = nullptr;
     struct Ft8SoftRec *d_soft = nullptr;  // [max_cand], FT8 channels while cwslg_enable_ft8_softbits is on (part of d_block)
+    struct Ft8MsgRec *d_msg = nullptr;    // [max_cand], FT8 channels while soft bits AND cwslg_enable_ft8_decode are on (part of d_block, behind d_soft)
     int nbins = 0, max_cand = 0;
     bool ft4 = false;                     // FT4 layout: spectra [122][FT4_ROW]; red = normalised savsm, red2 = sbase
     // FT4 coherent sync (ft4sync_kernels.hpp): frame spectrum, its stage-A scratch, refined records
@@ -105,6 +110,7 @@ inline void sync_free_shared(SyncShared &s)
     if (s.d_win) (void)hipFree(s.d_win);
     if (s.d_ft4c) (void)hipFree(s.d_ft4c);
     if (s.d_ft4c_win) (void)hipFree(s.d_ft4c_win);
+    if (s.d_ldpc) (void)hipFree(s.d_ldpc);
     s = SyncShared();
 }
 

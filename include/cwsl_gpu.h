@@ -417,6 +417,59 @@ int cwslg_fetch_ft4_sync(cwslg_ctx *ctx, int ch_id, cwslg_ft4_sync *dst, int max
 typedef struct { float llr[174]; float sigma; int32_t nsync; } cwslg_ft8_soft;   /* 704 bytes */
 int cwslg_enable_ft8_softbits(cwslg_ctx *ctx, int enable);
 int cwslg_fetch_ft8_softbits(cwslg_ctx *ctx, int ch_id, cwslg_ft8_soft *dst, int max, int *n, uint64_t *start_epoch);
+/* FT8 decode (row a13; PARITY UNPINNED): flooding sum-product decoding of the LDPC(174,91) code on the 174 metrics of every cwslg_ft8_soft record,
+ * then the CRC-14 -- the first consumer of those metrics, on the device: per candidate 91 bits, "is a codeword", "CRC matches" and an iteration
+ * count (20 bytes) instead of 704 bytes over the link and belief propagation on the host.  Structured like upstream bpdecode174_91.  Out of scope:
+ * ordered-statistics decoding, a-priori passes, signal subtraction, unpacking the 77 bits into text, de-duplication (neighbouring candidates of
+ * one transmission repeat one message).  Off by default; while it is off nothing changes (launches, buffers, upload bytes, lists, records).
+ *   The code is DATA THE CALLER LOADS: the WSJT-X source is not part of this repository and its parity-check table is not reproduced here.
+ *       cwslg_set_ldpc_code takes the 83 x 7 table `Nm` of the integrator's own WSJT-X tree (recalled, not checked here, as lib/ft8/ldpc_174_91_c_parity.f90), row-major: entry =
+ *       1-based codeword position 1..174, a row of weight 6 ends in one 0.  Validation: every position 1..174 occurs exactly three times; row
+ *       weights are 6 or 7; zeros occur only as the last entry of a row; no position occurs twice in a row -- anything else is CWSLG_ERR_ARG and
+ *       the loaded code, if any, stays.  Derived: per bit n its three checks in ascending row order c(n,0) < c(n,1) < c(n,2).  May be called
+ *       again at any time; the new table applies to every launch queued after the call.  The call drains the context's streams and copies
+ *       synchronously: it stalls the pipeline, so load a table once, not per slot.  Nothing in the kernel depends on which table it is.
+ *   Arithmetic: every operation is ONE un-fused float32 operation, `/` correctly rounded.  Row m's edges are its entries in the caller's order,
+ *       e = 0..w_m - 1; v[n][k] is the message from check c(n,k) to bit n, all +0 at the start.  The metrics are expected to be finite.
+ *       State ncnt = 0, nclast = 0.  For it = 0, 1, ...:
+ *         1. z[n] = ((llr[n] + v[n][0]) + v[n][1]) + v[n][2]; cw[n] = z[n] > 0.
+ *         2. nbad = number of rows whose cw over their entries has odd parity.
+ *         3. nbad == 0: exit, iters = it.
+ *         4. it == max_iter: exit, iters = max_iter.
+ *         5. it > 0: nd = nbad - nclast; ncnt = nd < 0 ? 0 : ncnt + 1; if ncnt >= 5 && it >= 10 && nbad > 15: exit, iters = it.
+ *         6. nclast = nbad.
+ *         7. every edge (m, e), n its bit, k the slot of m in n: t[m][e] = T(-0.5f * (z[n] - v[n][k])).
+ *         8. every edge: p = product of t[m][e'] over e' != e in ascending e', starting from 1.0f; v[n][k] = 2.0f * A(-p).
+ *       T(x): a = |x|; a >= 4.97f: 1.0f; otherwise x2 = a a, r = (a (945 + x2 (105 + x2))) / (945 + x2 (420 + x2 15)) (the [5/4] Pade form of
+ *           tanh), r = fminf(r, 1.0f); the result is copysignf(r, x).
+ *       A(y): z = |y|; z <= 0.664f: z / 0.83f; z <= 0.9217f: (z - 0.4064f) / 0.322f; z <= 0.9951f: (z - 0.8378f) / 0.0524f;
+ *           z <= 0.9998f: (z - 0.9914f) / 0.0012f; otherwise 7.0f; the result is copysignf(., y).
+ *   CRC-14: polynomial 0x2757 (x^14 implicit), bit-serial, MSB first, initial remainder 0, over bits 0..76 followed by 5 zero bits and then 14
+ *       augmenting zero bits (the remainder of M(x) x^14 for the 82-bit M); crc_ok means that remainder, MSB first, equals bits 77..90 AND
+ *       nbad == 0.  A consumer who needs another convention has all 91 bits and nbad.
+ *   Record: bits = codeword positions 0..90 at exit (whether or not a codeword), MSB first; nharderr = #{t < 174 : (llr[t] > 0) != cw[t]}.
+ *       A candidate whose nsync < min_nsync or whose sigma == 0 is NOT ATTEMPTED: iters = nbad = nharderr = -1, zero bits, crc_ok = 0.
+ * cwslg_enable_ft8_decode(ctx, 1, max_iter 1..200 (upstream 30), min_nsync 0..22 (upstream 7)) returns CWSLG_ERR_ARG unless a code is loaded,
+ * the sync stage is on and FT8 soft bits are on; switching it off is always allowed.  A boundary makes decode records only when soft bits and
+ * decode are both on at that boundary: one launch behind the soft-bit launch, the candidate count read on the device.  That launch is counted in
+ * stats.sync_launches (two per boundary with the decode on): sync_ms / sync_launches is then HALF the per-boundary time.  cwslg_fetch_ft8_decode behaves like cwslg_fetch_ft8_softbits: same ticket, record q belongs to list entry q, *n = min(list length,
+ * max), CWSLG_ERR_MODE for a channel that is not FT8, CWSLG_ERR_NO_FRAME unless decode records, soft-bit records, list and frame are of one
+ * epoch -- after a boundary that ran with the feature off there is nothing to fetch, never an older slot's records under a newer epoch.
+ * cwslg_ldpc_decode runs the same kernel on n >= 0 caller-supplied sets of 174 metrics (host memory) with no nsync filter, synchronously; it
+ * returns CWSLG_ERR_ARG without a loaded code.  It is the in-process path for FT4: fetch cwslg_ft4_soft, pass the sets you want; upstream's
+ * rvec descrambling of the 77 message bits stays with the consumer. */
+typedef struct {
+    uint8_t bits[12];     /* codeword positions 0..90 at exit, MSB first: bit t = bits[t>>3] & (0x80 >> (t&7)); the last 5 bits are 0 */
+    int16_t iters;        /* iterations run; 0 = the hard decision of the llr was already a codeword; -1 = not attempted            */
+    int16_t nbad;         /* unsatisfied checks at exit; 0 = a codeword; -1 when not attempted                                      */
+    int16_t nharderr;     /* #{t < 174 : (llr[t] > 0) != cw[t]} at exit; -1 when not attempted                                      */
+    uint8_t crc_ok;       /* nbad == 0 and the CRC-14 of bits 0..76 equals bits 77..90                                              */
+    uint8_t pad_;
+} cwslg_ft8_msg;          /* 20 bytes */
+int cwslg_set_ldpc_code(cwslg_ctx *ctx, const uint8_t *nm /* [83*7] */);
+int cwslg_enable_ft8_decode(cwslg_ctx *ctx, int enable, int max_iter, int min_nsync);
+int cwslg_fetch_ft8_decode(cwslg_ctx *ctx, int ch_id, cwslg_ft8_msg *dst, int max, int *n, uint64_t *start_epoch);
+int cwslg_ldpc_decode(cwslg_ctx *ctx, const float *llr /* [n][174] */, int n, int max_iter, cwslg_ft8_msg *out);
 /* FT4 soft bits (row a13; PARITY UNPINNED, restated from upstream ft4_decode's last stage before LDPC: the final ft4_downsample at the corrected
  * frequency, get_ft4_bitmetrics' three metric sets, the sync-quality counts nsync / nqual, normalizebmet, scalefac = 2.83).  One record per
  * cwslg_ft4_sync record of the SAME epoch, in the same order -- candidate order, then segment order: record q belongs to entry q of

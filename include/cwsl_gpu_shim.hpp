@@ -58,6 +58,16 @@ public:
     void enableFt8Softbits(bool enable = true) { check(c_, cwslg_enable_ft8_softbits(c_, enable ? 1 : 0)); }
     // soft bits per refined FT4 sync record from the next boundary on (needs the sync stage; records only while the coherent stage runs) -- SsbChannel::fetchFt4Softbits
     void enableFt4Softbits(bool enable = true) { check(c_, cwslg_enable_ft4_softbits(c_, enable ? 1 : 0)); }
+    // FT8 decode: the (174, 91) parity-check table is the caller's data -- nm[83 * 7], the Nm table of the integrator's own WSJT-X tree
+    // (cwslg_set_ldpc_code validates it); then LDPC decode + CRC-14 per FT8 sync candidate from the next boundary on (needs a loaded code, the sync
+    // stage and FT8 soft bits) -- SsbChannel::fetchFt8Decode; ldpcDecode runs the same kernel on caller-supplied metrics (the FT4 path)
+    void setLdpcCode(const std::uint8_t *nm) { check(c_, cwslg_set_ldpc_code(c_, nm)); }
+    void enableFt8Decode(bool enable = true, int maxIter = 30, int minNsync = 7) { check(c_, cwslg_enable_ft8_decode(c_, enable ? 1 : 0, maxIter, minNsync)); }
+    void ldpcDecode(const float *llr, int n, std::vector<cwslg_ft8_msg> &out, int maxIter = 30)
+    {
+        out.resize(n);
+        check(c_, cwslg_ldpc_decode(c_, llr, n, maxIter, out.data()));
+    }
     void synchronize() { check(c_, cwslg_synchronize(c_)); }
     // One block for each of several receivers in ONE call (cwslg_push_iq_many): for a host that serves thousands of streams, where a
     // per-receiver push per block (Receiver.hpp:242-249, ReceiverPort::push below) would mean hundreds of thousands of copies a second.
@@ -183,6 +193,18 @@ public:
         out.resize(max);
         int n = 0;
         const int rc = cwslg_fetch_ft8_softbits(ctx_.raw(), id_, out.data(), max, &n, startEpoch);
+        if (rc == CWSLG_ERR_NO_FRAME) { out.clear(); return 0; }
+        check(ctx_.raw(), rc);
+        out.resize(n);
+        return n;
+    }
+    // FT8 channels with Context::enableFt8Decode: record q (91 bits, iters, nbad, nharderr, crc_ok) belongs to entry q of candidates() of the same
+    // epoch -- cwslg_fetch_ft8_decode; 0 records while none of the current epoch exist
+    int fetchFt8Decode(std::vector<cwslg_ft8_msg> &out, int max = 600, std::uint64_t *startEpoch = nullptr)
+    {
+        out.resize(max);
+        int n = 0;
+        const int rc = cwslg_fetch_ft8_decode(ctx_.raw(), id_, out.data(), max, &n, startEpoch);
         if (rc == CWSLG_ERR_NO_FRAME) { out.clear(); return 0; }
         check(ctx_.raw(), rc);
         out.resize(n);
