@@ -102,6 +102,22 @@ class Ft8Msg(C.Structure):
 FT8_MSG_DTYPE = np.dtype([("bits", np.uint8, 12), ("iters", np.int16), ("nbad", np.int16), ("nharderr", np.int16), ("crc_ok", np.uint8), ("pad_", np.uint8)])
 
 
+class Ft4Msg(C.Structure):
+    _fields_ = [("set", Ft8Msg * 3)]
+
+
+# numpy view of cwslg_ft4_msg (60 bytes): three FT8_MSG_DTYPE records -- rec["set"]["crc_ok"][q, s] is set s of record q
+FT4_MSG_DTYPE = np.dtype([("set", FT8_MSG_DTYPE, 3)])
+
+
+def ft4_best_set(rec):
+    """The set a consumer takes from FT4 decode records (FT4_MSG_DTYPE): upstream tries the metric sets in order and stops at the first success,
+    which is the smallest s with crc_ok; -1 if none.  One record -> int, an array of records -> int array."""
+    ok = np.asarray(rec["set"]["crc_ok"]) != 0
+    best = np.where(ok.any(axis=-1), ok.argmax(axis=-1), -1)
+    return int(best) if best.ndim == 0 else best.astype(np.int64)
+
+
 class Ft4Soft(C.Structure):
     _fields_ = [("llr", (C.c_float * 174) * 3), ("sigma", C.c_float * 3), ("nsync", C.c_int32), ("nqual", C.c_int32), ("pad_", C.c_int32)]
 
@@ -147,7 +163,7 @@ ABI_SYMBOLS = [
     "cwslg_synchronize", "cwslg_fetch_frame", "cwslg_fetch_slot", "cwslg_write_wav", "cwslg_fetch_audio_f32", "cwslg_frame_device_ptrs",
     "cwslg_enable_sync", "cwslg_set_candidate_order", "cwslg_fetch_candidates", "cwslg_set_ft4_syncmin", "cwslg_enable_ft4_coherent", "cwslg_fetch_ft4_sync",
     "cwslg_enable_ft8_softbits", "cwslg_fetch_ft8_softbits", "cwslg_enable_ft4_softbits", "cwslg_fetch_ft4_softbits", "cwslg_sync_debug_fetch", "cwslg_get_stats", "cwslg_reset_stats",
-    "cwslg_set_ldpc_code", "cwslg_enable_ft8_decode", "cwslg_fetch_ft8_decode", "cwslg_ldpc_decode",
+    "cwslg_set_ldpc_code", "cwslg_enable_ft8_decode", "cwslg_fetch_ft8_decode", "cwslg_ldpc_decode", "cwslg_enable_ft4_decode", "cwslg_fetch_ft4_decode",
     "cwslg_set_timing", "cwslg_demod_kernel_name", "cwslg_stream", "cwslg_channel_constants", "cwslg_phasor_checkpoint_stride", "cwslg_channel_phasor_checkpoints",
     "cwslg_slot_clock_next", "cwslg_pool_sizing", "cwslg_find_band", "cwslg_parse_decode_line",
     "cwslg_decoder_block_bytes", "cwslg_decoder_block_field", "cwslg_fill_decoder_block", "cwslg_decoder_route", "cwslg_decoder_command",
@@ -241,6 +257,8 @@ def load_library(build_if_missing=True):
     L.cwslg_ldpc_decode.argtypes = [vp, vp, i32, i32, vp]
     L.cwslg_enable_ft4_softbits.argtypes = [vp, i32]
     L.cwslg_fetch_ft4_softbits.argtypes = [vp, i32, C.POINTER(Ft4Soft), i32, C.POINTER(i32), C.POINTER(u64)]
+    L.cwslg_enable_ft4_decode.argtypes = [vp, i32, i32, i32, i32]
+    L.cwslg_fetch_ft4_decode.argtypes = [vp, i32, C.POINTER(Ft4Msg), i32, C.POINTER(i32), C.POINTER(u64)]
     L.cwslg_sync_debug_fetch.argtypes = [vp, i32, i32, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(i32)]
     L.cwslg_get_stats.argtypes = [vp, C.POINTER(Stats)]
     L.cwslg_reset_stats.argtypes = [vp]
@@ -678,6 +696,25 @@ class Context:
         out = (np.ascontiguousarray(rec[:, :522]).reshape(-1, 3, 174), np.ascontiguousarray(rec[:, 522:525]),
                rec[:, 525].copy().view(np.int32), rec[:, 526].copy().view(np.int32))
         return out + (t0.value,) if with_epoch else out
+
+    def enable_ft4_decode(self, enable=True, max_iter=30, min_nsync=8, min_nqual=20):
+        """LDPC decode + CRC-14 on the three metric sets of every FT4 soft-bit record (cwslg_ft4_msg); needs a loaded code, enable_sync and
+        enable_ft4_softbits; applies from the next boundary on."""
+        self._chk(self.L.cwslg_enable_ft4_decode(self.h, int(enable), int(max_iter), int(min_nsync), int(min_nqual)))
+
+    def fetch_ft4_decode(self, ch, max_rec=1800, with_epoch=False):
+        """-> None unless decode records of the channel's current epoch exist, else a numpy record array (FT4_MSG_DTYPE: rec["set"][q, s] is the
+        FT8_MSG_DTYPE record of metric set s) whose row q belongs to entry q of fetch_ft4_sync of the same epoch (with_epoch: (records, frame
+        start epoch)).  ft4_best_set picks the set upstream would take."""
+        buf = np.zeros(max(int(max_rec), 1), FT4_MSG_DTYPE)
+        n = C.c_int()
+        t0 = C.c_uint64()
+        rc = self.L.cwslg_fetch_ft4_decode(self.h, ch, buf.ctypes.data_as(C.POINTER(Ft4Msg)), int(max_rec), C.byref(n), C.byref(t0))
+        if rc == ERR_NO_FRAME:
+            return None
+        self._chk(rc)
+        rec = buf[:n.value].copy()
+        return (rec, t0.value) if with_epoch else rec
 
     def enable_long_sync(self, on=True, nfa_hz=1400, nfb_hz=1600, minsync=1.2):
         """Candidate search of the 120 s modes (WSPR: wsprd's front end; FST4W-120: get_candidates_fst4 over nfa..nfb)."""

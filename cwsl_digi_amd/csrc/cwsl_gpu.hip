@@ -205,6 +205,7 @@ struct Channel {
     uint64_t soft_t0 = 0;              // ... the FT8 soft-bit records were computed from (cwslg_enable_ft8_softbits; 0: none)
     uint64_t soft4_t0 = 0;             // ... the FT4 soft-bit records were computed from (cwslg_enable_ft4_softbits; 0: none)
     uint64_t msg_t0 = 0;               // ... the FT8 decode records were computed from (cwslg_enable_ft8_decode; 0: none)
+    uint64_t msg4_t0 = 0;              // ... the FT4 decode records were computed from (cwslg_enable_ft4_decode; 0: none)
     SyncChannelBuffers syncbuf;
 };
 

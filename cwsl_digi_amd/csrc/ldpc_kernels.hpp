@@ -17,10 +17,15 @@
 // The two sides meet in a wave-private LDS image: v[83][8] (an edge's position is 8 m + e) and z[192], 3.4 KB per wave.  Nothing is shared
 // between waves, hence no workgroup barrier; every exit is wave-uniform (nbad comes from ballots).
 // The same kernel serves cwslg_ldpc_decode: works == nullptr, n_flat sets of 174 metrics from llr_flat, no nsync filter.
+// And the FT4 decode (cwslg_enable_ft4_decode), a third way of finding llr and out in front of the same loop: works4 != nullptr, one wave per
+// (record slot, metric set) of ft4_softbits_kernel's slot array, grid (ceil(9 max_cand / 4), FT4 channels).  Wave q of a channel: slot = q / 3,
+// set s = q % 3, cand = slot / 3, r = slot % 3; it leaves if q >= 9 max_cand, cand >= min(*ncand, max_cand) or r >= nrec[cand] -- the reads
+// ft4_softbits_kernel makes, on the device -- and writes set[s] of the slot's cwslg_ft4_msg (three cwslg_ft8_msg: record q of the channel's array).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "ldpc_host.hpp"
+#include "ft4soft_kernels.hpp"
 
 namespace cwslg {
 
@@ -28,6 +33,8 @@ constexpr int LDPC_WAVES = 4;
 typedef unsigned v2u __attribute__((ext_vector_type(2)));
 struct Ft8MsgRec { uint8_t bits[12]; int16_t iters, nbad, nharderr; uint8_t crc_ok, pad_; };    // = cwslg_ft8_msg
 static_assert(sizeof(Ft8MsgRec) == 20, "cwslg_ft8_msg is 20 bytes");
+struct Ft4MsgRec { Ft8MsgRec set[3]; };                                                          // = cwslg_ft4_msg
+static_assert(sizeof(Ft4MsgRec) == 60, "cwslg_ft4_msg is 60 bytes");
 constexpr int LDPC_VSIZE = LDPC_M * LDPC_EPITCH;       // 664 message slots
 constexpr int LDPC_ZDUMMY = 191;                       // where an absent edge reads its z (a zero nobody writes)
 
@@ -98,7 +105,9 @@ __device__ __forceinline__ void ldpc_row_update(LdpcRow &r, float *s_v, int m)
 __global__ __launch_bounds__(64 * LDPC_WAVES) void ldpc_decode_kernel(const SyncWork *__restrict__ works, Ft8SoftRec *const *__restrict__ soft,
                                                                       Ft8MsgRec *const *__restrict__ msg, const float *__restrict__ llr_flat,
                                                                       Ft8MsgRec *__restrict__ out_flat, int n_flat, int maxcand, int max_iter, int min_nsync,
-                                                                      const LdpcTables *__restrict__ tables)
+                                                                      const LdpcTables *__restrict__ tables, const Ft4Work *__restrict__ works4,
+                                                                      Ft4SoftRec *const *__restrict__ soft4, Ft4MsgRec *const *__restrict__ msg4,
+                                                                      int min_nqual)
 {
     __shared__ __attribute__((aligned(16))) float s_vall[LDPC_WAVES][LDPC_VSIZE];
     __shared__ __attribute__((aligned(16))) float s_zall[LDPC_WAVES][192];
@@ -115,6 +124,16 @@ __global__ __launch_bounds__(64 * LDPC_WAVES) void ldpc_decode_kernel(const Sync
         llr = rec->llr;
         out = as_global_rw(msg[blockIdx.y]) + q;
         attempt = rec->nsync >= min_nsync && rec->sigma != 0.0f;
+    } else if (works4) {
+        const Ft4Work *w = works4 + blockIdx.y;
+        if (q >= 9 * maxcand) return;                          // wave-uniform, all three
+        const int slot = q / 3, s = q - 3 * slot, cand = slot / 3, r = slot - 3 * cand;
+        if (cand >= min(*as_global(w->ncand), maxcand)) return;
+        if (r >= as_global(w->nrec)[cand]) return;
+        const CWSLG_GLOBAL Ft4SoftRec *rec = as_global(soft4[blockIdx.y]) + slot;
+        llr = rec->llr[s];
+        out = as_global_rw(&msg4[blockIdx.y]->set[0]) + q;     // set s of slot q / 3
+        attempt = rec->nsync >= min_nsync && rec->nqual >= min_nqual && rec->sigma[s] != 0.0f;
     } else {
         if (q >= n_flat) return;
         llr = as_global(llr_flat) + (size_t)q * LDPC_N;

@@ -149,6 +149,18 @@ int ft4s_ensure_channel(cwslg_ctx *c, Channel &ch, bool want)
     return CWSLG_OK;
 }
 
+// The FT4 decode records (ldpc_kernels.hpp), [max_cand][3] cwslg_ft4_msg in the soft records' slot order, under the soft records' rules: they
+// exist only while the feature is on and follow max_cand (sync_ensure_channel frees everything when it changes).
+int ft4m_ensure_channel(cwslg_ctx *c, Channel &ch, bool want)
+{
+    SyncChannelBuffers &b = ch.syncbuf;
+    if ((b.d_ft4msg != nullptr) == want) return CWSLG_OK;
+    ch.msg4_t0 = 0;
+    if (!want) { (void)hipFree(b.d_ft4msg); b.d_ft4msg = nullptr; return CWSLG_OK; }
+    HIPCHK(c, hipMalloc((void **)&b.d_ft4msg, (size_t)b.max_cand * 3 * sizeof(Ft4MsgRec)));
+    return CWSLG_OK;
+}
+
 int sync_ensure_channel(cwslg_ctx *c, Channel &ch)
 {
     SyncChannelBuffers &b = ch.syncbuf;
@@ -163,6 +175,7 @@ int sync_ensure_channel(cwslg_ctx *c, Channel &ch)
     ch.soft_t0 = 0;
     ch.msg_t0 = 0;
     ch.soft4_t0 = 0;
+    ch.msg4_t0 = 0;
     const size_t sp = ((size_t)(ch.sync_ft4 ? FT4_NHSYM : FT8_NHSYM) * want_bins * sizeof(float) + 255) & ~size_t(255);
     const size_t vec = ((size_t)(FT8_NH1 + 1) * 4 + 255) & ~size_t(255);
     const size_t cand = ((size_t)cfg.max_cand * sizeof(SyncChannelBuffers::Cand) + 255) & ~size_t(255);
@@ -186,6 +199,31 @@ int sync_ensure_channel(cwslg_ctx *c, Channel &ch)
     return CWSLG_OK;
 }
 
+// ldpc_decode_kernel's three addressing modes, one launcher each: what a mode does not use is null / 0 here and nowhere else.
+//   FT8 chain: one wave per candidate of n_chan channels, records behind the soft-bit records
+void ldpc_launch_ft8(hipStream_t st, const void *tables, const SyncWork *works, Ft8SoftRec *const *soft, Ft8MsgRec *const *msg, size_t n_chan, int max_cand,
+                     int max_iter, int min_nsync)
+{
+    hipLaunchKernelGGL(ldpc_decode_kernel, dim3((unsigned)((max_cand + LDPC_WAVES - 1) / LDPC_WAVES), (unsigned)n_chan), dim3(64 * LDPC_WAVES), 0, st, works, soft, msg,
+                       (const float *)nullptr, (Ft8MsgRec *)nullptr, 0, max_cand, max_iter, min_nsync, (const LdpcTables *)tables, (const Ft4Work *)nullptr,
+                       (Ft4SoftRec *const *)nullptr, (Ft4MsgRec *const *)nullptr, 0);
+}
+//   flat: n sets of 174 metrics, no gate
+void ldpc_launch_flat(hipStream_t st, const void *tables, const float *llr, Ft8MsgRec *out, int n, int max_iter)
+{
+    hipLaunchKernelGGL(ldpc_decode_kernel, dim3((unsigned)((n + LDPC_WAVES - 1) / LDPC_WAVES), 1), dim3(64 * LDPC_WAVES), 0, st, (const SyncWork *)nullptr,
+                       (Ft8SoftRec *const *)nullptr, (Ft8MsgRec *const *)nullptr, llr, out, n, 0, max_iter, 0, (const LdpcTables *)tables, (const Ft4Work *)nullptr,
+                       (Ft4SoftRec *const *)nullptr, (Ft4MsgRec *const *)nullptr, 0);
+}
+//   FT4 chain: one wave per (record slot, metric set) of n_chan channels, 9 max_cand waves per channel
+void ldpc_launch_ft4(hipStream_t st, const void *tables, const Ft4Work *works4, Ft4SoftRec *const *soft4, Ft4MsgRec *const *msg4, size_t n_chan, int max_cand,
+                     int max_iter, int min_nsync, int min_nqual)
+{
+    hipLaunchKernelGGL(ldpc_decode_kernel, dim3((unsigned)((9 * max_cand + LDPC_WAVES - 1) / LDPC_WAVES), (unsigned)n_chan), dim3(64 * LDPC_WAVES), 0, st,
+                       (const SyncWork *)nullptr, (Ft8SoftRec *const *)nullptr, (Ft8MsgRec *const *)nullptr, (const float *)nullptr, (Ft8MsgRec *)nullptr, 0, max_cand,
+                       max_iter, min_nsync, (const LdpcTables *)tables, works4, soft4, msg4, min_nqual);
+}
+
 // Run the sync stage on the frames finalised by this boundary: FT8 channels through the Costas search, FT4
 // channels through getcandidates4's spectral-peak search.  Other modes have no sync stage.
 int sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
@@ -196,6 +234,7 @@ int sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
     std::vector<SyncWork> works8, works4;
     std::vector<Ft4Work> works4c;
     std::vector<Ft4SoftRec *> soft4;                          // cwslg_enable_ft4_softbits: one record array per FT4 channel, in works4c's order
+    std::vector<Ft4MsgRec *> msg4;                            // cwslg_enable_ft4_decode (with the coherent stage and soft bits on): one record array per FT4 channel, in works4c's order
     std::vector<Ft8SoftRec *> soft8;                          // cwslg_enable_ft8_softbits: one record array per FT8 channel, in works8's order
     std::vector<Ft8MsgRec *> msg8;                            // cwslg_enable_ft8_decode (with soft bits on): one record array per FT8 channel, in works8's order
     for (int id : emitted) {
@@ -231,9 +270,14 @@ int sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
         if (ch.sync_ft4) {
             const bool soft = cfg.ft4_coherent && cfg.ft4_soft;
             if ((rc = ft4s_ensure_channel(c, ch, soft)) != CWSLG_OK) return rc;
+            if ((rc = ft4m_ensure_channel(c, ch, soft && cfg.ft4_decode)) != CWSLG_OK) return rc;
             if (soft) {
                 soft4.push_back(ch.syncbuf.d_ft4soft);
                 ch.soft4_t0 = ch.frame_t0;                    // the soft-bit records now queued belong to this frame (feature or coherent stage off: the OLD epoch stays, nothing to fetch)
+                if (cfg.ft4_decode) {
+                    msg4.push_back(ch.syncbuf.d_ft4msg);
+                    ch.msg4_t0 = ch.frame_t0;                 // ... and the decode records, under the same rule
+                }
             }
         }
     }
@@ -257,19 +301,19 @@ int sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
         // the decode: one wave per candidate behind the metrics it reads (same grid, same device-side count); counted as a launch of its own
         if (msg8.empty()) return;
         Ft8SoftRec *const *dsoft = (Ft8SoftRec *const *)((const SyncWork *)wb->d + n8 + n4);
-        hipLaunchKernelGGL(ldpc_decode_kernel, dim3((unsigned)((cfg.max_cand + LDPC_WAVES - 1) / LDPC_WAVES), (unsigned)n8), dim3(64 * LDPC_WAVES), 0, st,
-                           (const SyncWork *)wb->d, dsoft, (Ft8MsgRec *const *)(dsoft + n8), (const float *)nullptr, (Ft8MsgRec *)nullptr, 0, cfg.max_cand,
-                           cfg.ldpc_max_iter, cfg.ldpc_min_nsync, (const LdpcTables *)c->sync_shared.d_ldpc);
+        ldpc_launch_ft8(st, c->sync_shared.d_ldpc, (const SyncWork *)wb->d, dsoft, (Ft8MsgRec *const *)(dsoft + n8), n8, cfg.max_cand, cfg.ldpc_max_iter,
+                        cfg.ldpc_min_nsync);
         c->stats.sync_launches++;
     };
     WorkBuf *wb4 = nullptr;
     if (!works4c.empty()) {
         // (the FT4 soft-bit launch's record pointers ride behind the descriptors, as the FT8 ones do above)
-        const size_t wb4_bytes = works4c.size() * sizeof(Ft4Work) + soft4.size() * sizeof(Ft4SoftRec *);
+        const size_t wb4_bytes = works4c.size() * sizeof(Ft4Work) + soft4.size() * sizeof(Ft4SoftRec *) + msg4.size() * sizeof(Ft4MsgRec *);
         wb4 = acquire_workbuf(c, wb4_bytes);
         if (!wb4) return fail(c, CWSLG_ERR_NOMEM, "work buffer allocation failed");
         std::memcpy(wb4->h, works4c.data(), works4c.size() * sizeof(Ft4Work));
         if (!soft4.empty()) std::memcpy((Ft4Work *)wb4->h + works4c.size(), soft4.data(), soft4.size() * sizeof(Ft4SoftRec *));
+        if (!msg4.empty()) std::memcpy((Ft4SoftRec **)((Ft4Work *)wb4->h + works4c.size()) + soft4.size(), msg4.data(), msg4.size() * sizeof(Ft4MsgRec *));
         HIPCHK(c, upload_workbuf(c, wb4, wb4_bytes));
     }
     hipEvent_t ea, eb;
@@ -413,6 +457,14 @@ int sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
             if (!soft4.empty())
                 hipLaunchKernelGGL(ft4_softbits_kernel, dim3(3u * (unsigned)cfg.max_cand, (unsigned)n4), dim3(256), 0, c->stream, f4,
                                    (Ft4SoftRec *const *)(f4 + works4c.size()), c->ft4_tables, c->sync_shared.ft4_w32, cfg.max_cand);
+            // the decode: one wave per (record slot, metric set) behind the metrics it reads, the counts read on the device as the launch above
+            // reads them; counted as a launch of its own, as the FT8 decode's is
+            if (!msg4.empty()) {
+                Ft4SoftRec *const *dsoft4 = (Ft4SoftRec *const *)(f4 + works4c.size());
+                ldpc_launch_ft4(c->stream, c->sync_shared.d_ldpc, f4, dsoft4, (Ft4MsgRec *const *)(dsoft4 + soft4.size()), n4, cfg.max_cand, cfg.ldpc4_max_iter,
+                                cfg.ldpc4_min_nsync, cfg.ldpc4_min_nqual);
+                c->stats.sync_launches++;
+            }
         }
     }
     if (chain_async) {
@@ -463,6 +515,8 @@ int cwslg_enable_sync(cwslg_ctx *c, int enable, float syncmin, int max_cand, int
         cfg.ft8_soft = c->sync_cfg.ft8_soft;
         cfg.ft4_soft = c->sync_cfg.ft4_soft;
         cfg.ft8_decode = c->sync_cfg.ft8_decode; cfg.ldpc_max_iter = c->sync_cfg.ldpc_max_iter; cfg.ldpc_min_nsync = c->sync_cfg.ldpc_min_nsync;
+        cfg.ft4_decode = c->sync_cfg.ft4_decode; cfg.ldpc4_max_iter = c->sync_cfg.ldpc4_max_iter; cfg.ldpc4_min_nsync = c->sync_cfg.ldpc4_min_nsync;
+        cfg.ldpc4_min_nqual = c->sync_cfg.ldpc4_min_nqual;
         if (cfg.ft8_soft) cfg.nbins = (cfg.ib + 15 + 31) / 32 * 32;   // soft bits on: tone 7 of bin ib (ib + 14) lies inside the row
         hipSetDevice(c->device);
         cfg.ft4_coherent = c->sync_cfg.ft4_coherent;
@@ -661,9 +715,7 @@ int cwslg_ldpc_decode(cwslg_ctx *c, const float *llr, int n, int max_iter, cwslg
     HIPCHK(c, hipMalloc((void **)&d, in_bytes + out_bytes));      // (in_bytes is a multiple of 8: the records behind it are aligned)
     hipError_t e = hipMemcpyAsync(d, llr, in_bytes, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(ldpc_decode_kernel, dim3((unsigned)((n + LDPC_WAVES - 1) / LDPC_WAVES), 1), dim3(64 * LDPC_WAVES), 0, c->stream,
-                           (const SyncWork *)nullptr, (Ft8SoftRec *const *)nullptr, (Ft8MsgRec *const *)nullptr, (const float *)d,
-                           (Ft8MsgRec *)(d + in_bytes), n, 0, max_iter, 0, (const LdpcTables *)c->sync_shared.d_ldpc);
+        ldpc_launch_flat(c->stream, c->sync_shared.d_ldpc, (const float *)d, (Ft8MsgRec *)(d + in_bytes), n, max_iter);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(out, d + in_bytes, out_bytes, hipMemcpyDeviceToHost, c->stream);
@@ -774,6 +826,67 @@ int cwslg_fetch_ft4_softbits(cwslg_ctx *c, int ch_id, cwslg_ft4_soft *dst, int m
     for (int k = 0; k < cnt; ++k)                               // candidate order, then segment order: entry q of cwslg_fetch_ft4_sync
         for (int q = 0; q < nrec[k] && q < 3; ++q) {
             if (out < max) std::memcpy(&dst[out], &rec[(size_t)k * 3 + q], sizeof(Ft4SoftRec));
+            ++out;
+        }
+    *n = std::min(out, max);
+    return CWSLG_OK;
+}
+
+// FT4 decode (ldpc_kernels.hpp's third addressing mode): the FT8 decode's rules with the FT4 soft bits in the place of the FT8 ones.
+int cwslg_enable_ft4_decode(cwslg_ctx *c, int enable, int max_iter, int min_nsync, int min_nqual)
+{
+    if (!c) return CWSLG_ERR_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    SyncConfig &cfg = c->sync_cfg;
+    if (!enable) { cfg.ft4_decode = false; return CWSLG_OK; }
+    if (max_iter < 1 || max_iter > 200 || min_nsync < 0 || min_nsync > 17 || min_nqual < 0 || min_nqual > 33)
+        return fail(c, CWSLG_ERR_ARG, "FT4 decode parameters out of range");
+    if (!c->sync_shared.ldpc_loaded) return fail(c, CWSLG_ERR_ARG, "FT4 decode needs a parity-check table (cwslg_set_ldpc_code)");
+    if (!cfg.enabled || !cfg.ft4_soft) return fail(c, CWSLG_ERR_ARG, "FT4 decode needs the sync stage and FT4 soft bits (cwslg_enable_sync, cwslg_enable_ft4_softbits)");
+    cfg.ft4_decode = true; cfg.ldpc4_max_iter = max_iter; cfg.ldpc4_min_nsync = min_nsync; cfg.ldpc4_min_nqual = min_nqual;
+    return CWSLG_OK;
+}
+
+// Handed out like the FT4 soft-bit records (the same nrec walk over the same slot layout), and only together with them: decode records, soft
+// records, sync records, list and frame of ONE epoch.
+int cwslg_fetch_ft4_decode(cwslg_ctx *c, int ch_id, cwslg_ft4_msg *dst, int max, int *n, uint64_t *start_epoch)
+{
+    if (!c || !n || (max > 0 && !dst)) return CWSLG_ERR_ARG;
+    *n = 0;
+    const int *cnt_src = nullptr, *nrec_src = nullptr;
+    const Ft4MsgRec *rec_src = nullptr;
+    int lim = 0;
+    ResultFetch rf;
+    {
+        std::lock_guard<std::mutex> g(c->mu);
+        if (ch_id < 0 || ch_id >= (int)c->chans.size() || !c->chans[ch_id].open) return fail(c, CWSLG_ERR_ARG, "bad channel id");
+        Channel &ch = c->chans[ch_id];
+        if (!ch.sync_ft4) return fail(c, CWSLG_ERR_MODE, "FT4 decode records exist for FT4 channels only (mode %s)", ch.mode.c_str());
+        if (!ch.have_frame || !ch.syncbuf.d_block || !ch.syncbuf.d_ft4c || !ch.syncbuf.d_ft4soft || !ch.syncbuf.d_ft4msg || !ch.msg4_t0 ||
+            ch.msg4_t0 != ch.frame_t0 || ch.msg4_t0 != ch.cand_t0 || ch.msg4_t0 != ch.soft4_t0)
+            return CWSLG_ERR_NO_FRAME;
+        hipSetDevice(c->device);
+        if (start_epoch) *start_epoch = ch.msg4_t0;
+        cnt_src = ch.syncbuf.d_ncand; nrec_src = ch.syncbuf.d_nrec; rec_src = ch.syncbuf.d_ft4msg; lim = ch.syncbuf.max_cand;
+        int rc = begin_result_fetch(c, ch, rf);
+        if (rc) return rc;
+    }
+    static_assert(sizeof(cwslg_ft4_msg) == sizeof(Ft4MsgRec), "record layout");
+    int cnt = 0;
+    HIPCHK(c, hipStreamWaitEvent(rf.fs, rf.ev, 0));
+    HIPCHK(c, hipMemcpyAsync(&cnt, cnt_src, sizeof(int), hipMemcpyDeviceToHost, rf.fs));
+    HIPCHK(c, hipStreamSynchronize(rf.fs));
+    cnt = std::max(0, std::min(cnt, lim));
+    if (cnt <= 0) return CWSLG_OK;
+    std::vector<int> nrec((size_t)cnt);
+    std::vector<Ft4MsgRec> rec((size_t)cnt * 3);
+    HIPCHK(c, hipMemcpyAsync(nrec.data(), nrec_src, (size_t)cnt * sizeof(int), hipMemcpyDeviceToHost, rf.fs));
+    HIPCHK(c, hipMemcpyAsync(rec.data(), rec_src, (size_t)cnt * 3 * sizeof(Ft4MsgRec), hipMemcpyDeviceToHost, rf.fs));
+    HIPCHK(c, hipStreamSynchronize(rf.fs));
+    int out = 0;
+    for (int k = 0; k < cnt; ++k)                               // candidate order, then segment order: entry q of cwslg_fetch_ft4_sync
+        for (int q = 0; q < nrec[k] && q < 3; ++q) {
+            if (out < max) std::memcpy(&dst[out], &rec[(size_t)k * 3 + q], sizeof(Ft4MsgRec));
             ++out;
         }
     *n = std::min(out, max);

@@ -47,6 +47,8 @@ struct SyncConfig {
     bool ft8_soft = false;                // cwslg_enable_ft8_softbits: soft bits per FT8 candidate (ft8soft_kernels.hpp); the row then holds tone 7 of bin ib (ib+15 rounded up)
     bool ft8_decode = false;              // cwslg_enable_ft8_decode: LDPC(174,91) decode + CRC-14 per FT8 candidate (ldpc_kernels.hpp); runs only while ft8_soft is on too
     int ldpc_max_iter = 30, ldpc_min_nsync = 7;
+    bool ft4_decode = false;              // cwslg_enable_ft4_decode: the same decode on the three metric sets of every FT4 soft-bit record; runs only while ft4_coherent and ft4_soft are on too
+    int ldpc4_max_iter = 30, ldpc4_min_nsync = 8, ldpc4_min_nqual = 20;
 };
 
 struct SyncTables {                       // device pointers: W_NZ, W_128, 0.5 W_2NZ twiddles, optional window
@@ -83,6 +85,7 @@ struct SyncChannelBuffers {
     void *d_rec = nullptr;                // Ft4Rec [max_cand][3]
     int *d_nrec = nullptr;                // [max_cand]
     struct Ft4SoftRec *d_ft4soft = nullptr;   // [max_cand][3], the slot layout of d_rec; an allocation of its own, only while cwslg_enable_ft4_softbits is on
+    struct Ft4MsgRec *d_ft4msg = nullptr;     // [max_cand][3], the same slot layout; an allocation of its own, only while soft bits AND cwslg_enable_ft4_decode are on
 };
 
 struct alignas(16) SyncWork {
@@ -102,6 +105,7 @@ inline void sync_free_channel(SyncChannelBuffers &b)
     if (b.d_block) (void)hipFree(b.d_block);
     if (b.d_ft4c) (void)hipFree(b.d_ft4c);
     if (b.d_ft4soft) (void)hipFree(b.d_ft4soft);
+    if (b.d_ft4msg) (void)hipFree(b.d_ft4msg);
     b = SyncChannelBuffers();
 }
 inline void sync_free_shared(SyncShared &s)

@@ -456,8 +456,9 @@ int cwslg_fetch_ft8_softbits(cwslg_ctx *ctx, int ch_id, cwslg_ft8_soft *dst, int
  * max), CWSLG_ERR_MODE for a channel that is not FT8, CWSLG_ERR_NO_FRAME unless decode records, soft-bit records, list and frame are of one
  * epoch -- after a boundary that ran with the feature off there is nothing to fetch, never an older slot's records under a newer epoch.
  * cwslg_ldpc_decode runs the same kernel on n >= 0 caller-supplied sets of 174 metrics (host memory) with no nsync filter, synchronously; it
- * returns CWSLG_ERR_ARG without a loaded code.  It is the in-process path for FT4: fetch cwslg_ft4_soft, pass the sets you want; upstream's
- * rvec descrambling of the 77 message bits stays with the consumer. */
+ * returns CWSLG_ERR_ARG without a loaded code.  It is the in-process path for FT4 metrics that are already on the host: fetch cwslg_ft4_soft, pass the
+ * sets you want; on the device the FT4 chain has a stage of its own, cwslg_enable_ft4_decode below, which needs no fetch and no round trip.
+ * Upstream's rvec descrambling of the 77 message bits stays with the consumer. */
 typedef struct {
     uint8_t bits[12];     /* codeword positions 0..90 at exit, MSB first: bit t = bits[t>>3] & (0x80 >> (t&7)); the last 5 bits are 0 */
     int16_t iters;        /* iterations run; 0 = the hard decision of the llr was already a codeword; -1 = not attempted            */
@@ -516,6 +517,31 @@ int cwslg_ldpc_decode(cwslg_ctx *ctx, const float *llr /* [n][174] */, int n, in
 typedef struct { float llr[3][174]; float sigma[3]; int32_t nsync; int32_t nqual; int32_t pad_; } cwslg_ft4_soft;   /* 2112 bytes */
 int cwslg_enable_ft4_softbits(cwslg_ctx *ctx, int enable);
 int cwslg_fetch_ft4_softbits(cwslg_ctx *ctx, int ch_id, cwslg_ft4_soft *dst, int max, int *n, uint64_t *start_epoch);
+/* FT4 decode (row a13; PARITY UNPINNED): the FT8 decode above on the three metric sets of every cwslg_ft4_soft record, on the device, behind the
+ * launch that has just written them -- per record three cwslg_ft8_msg (60 bytes) instead of 2112 bytes over the link, a choice of sets on the
+ * host and a blocking cwslg_ldpc_decode.  FT4 and FT8 share the LDPC(174,91) code and the CRC-14: the code is the one cwslg_set_ldpc_code
+ * loaded.  Off by default; while it is off nothing changes (launches, buffers, upload bytes, lists, records, frames).
+ *   Record: set[s], s = 0..2, is exactly what the contract of cwslg_ft8_msg above yields for llr[s][0..173] of the record's cwslg_ft4_soft: the
+ *       same arithmetic, the same exits, the same bits / iters / nbad / nharderr / crc_ok.  Nothing is restated or changed here.
+ *   Gates: a record whose nsync < min_nsync or whose nqual < min_nqual is NOT ATTEMPTED in all three sets (iters = nbad = nharderr = -1, zero
+ *       bits, crc_ok = 0).  Otherwise set s is not attempted exactly when sigma[s] == 0: its llr are all +0 then, which would "decode" to the
+ *       all-zero codeword.  The three sets of a record are decoded side by side, each to its own exit.
+ *   Which set "wins" is not stored.  Upstream tries the sets in order and stops at the first success: the smallest s with crc_ok
+ *       (cwslgpu::ft4BestSet in cwsl_gpu_shim.hpp, ft4_best_set in the Python package; -1 if none).
+ *   Out of scope: the rvec descrambling of the 77 message bits (the CRC is over the scrambled bits, so crc_ok does not need it), ordered-statistics
+ *       decoding and a-priori passes, unpacking to text, de-duplication, extending cwslg_fetch_slot.
+ * cwslg_enable_ft4_decode(ctx, 1, max_iter 1..200 (upstream 30), min_nsync 0..17 (upstream 8), min_nqual 0..33 (upstream 20)) returns
+ * CWSLG_ERR_ARG unless a code is loaded, the sync stage is on and FT4 soft bits are on; switching it off is always allowed.  min_nsync 17 or
+ * min_nqual 33 mean "nothing is attempted", as min_nsync 22 does for FT8.  A boundary makes decode records only when the coherent stage, FT4
+ * soft bits and the decode are all on at that boundary: one launch behind the soft-bit launch, the candidate and record counts read on the
+ * device.  That launch is counted in stats.sync_launches, as the FT8 decode's is (a boundary with FT4 channels alone then counts two: sync_ms /
+ * sync_launches is HALF the per-boundary time).  cwslg_fetch_ft4_decode behaves like cwslg_fetch_ft4_softbits: same ticket, record q belongs to
+ * entry q of cwslg_fetch_ft4_sync, *n = min(record count, max), CWSLG_ERR_MODE for a channel that is not FT4, CWSLG_ERR_NO_FRAME unless decode
+ * records, soft records, sync records, list and frame are of one epoch -- after a boundary that ran with the feature, the soft bits or the
+ * coherent stage off there is nothing to fetch, never an older slot's records under a newer epoch. */
+typedef struct { cwslg_ft8_msg set[3]; } cwslg_ft4_msg;          /* 60 bytes */
+int cwslg_enable_ft4_decode(cwslg_ctx *ctx, int enable, int max_iter, int min_nsync, int min_nqual);
+int cwslg_fetch_ft4_decode(cwslg_ctx *ctx, int ch_id, cwslg_ft4_msg *dst, int max, int *n, uint64_t *start_epoch);
 int cwslg_fetch_slot(cwslg_ctx *ctx, int ch_id, int16_t *frame, size_t cap, void *list, size_t list_bytes,
                      cwslg_ft4_sync *ft4, int max_ft4, cwslg_slot_result *out);
 int cwslg_set_ft4_syncmin(cwslg_ctx *ctx, float syncmin);

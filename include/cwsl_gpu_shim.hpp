@@ -43,6 +43,15 @@ inline void check(cwslg_ctx *c, int rc)
     throw std::runtime_error("libcwslgpu: " + msg);
 }
 
+// Which of a cwslg_ft4_msg's three sets a consumer takes: upstream tries the metric sets in order and stops at the first success, which is the
+// smallest s with crc_ok; -1 if none has it
+inline int ft4BestSet(const cwslg_ft4_msg &m)
+{
+    for (int s = 0; s < 3; ++s)
+        if (m.set[s].crc_ok) return s;
+    return -1;
+}
+
 class Context {
 public:
     explicit Context(int device = -1) { check(nullptr, cwslg_create(&c_, device)); }
@@ -67,6 +76,12 @@ public:
     {
         out.resize(n);
         check(c_, cwslg_ldpc_decode(c_, llr, n, maxIter, out.data()));
+    }
+    // FT4 decode: the same decode on the three metric sets of every FT4 soft-bit record from the next boundary on (needs a loaded code, the sync
+    // stage and FT4 soft bits; records only while the coherent stage runs) -- SsbChannel::fetchFt4Decode, ft4BestSet
+    void enableFt4Decode(bool enable = true, int maxIter = 30, int minNsync = 8, int minNqual = 20)
+    {
+        check(c_, cwslg_enable_ft4_decode(c_, enable ? 1 : 0, maxIter, minNsync, minNqual));
     }
     void synchronize() { check(c_, cwslg_synchronize(c_)); }
     // One block for each of several receivers in ONE call (cwslg_push_iq_many): for a host that serves thousands of streams, where a
@@ -205,6 +220,18 @@ public:
         out.resize(max);
         int n = 0;
         const int rc = cwslg_fetch_ft8_decode(ctx_.raw(), id_, out.data(), max, &n, startEpoch);
+        if (rc == CWSLG_ERR_NO_FRAME) { out.clear(); return 0; }
+        check(ctx_.raw(), rc);
+        out.resize(n);
+        return n;
+    }
+    // FT4 channels with Context::enableFt4Decode: record q (three cwslg_ft8_msg, one per metric set) belongs to entry q of cwslg_fetch_ft4_sync of
+    // the same epoch -- cwslg_fetch_ft4_decode; 0 records while none of the current epoch exist
+    int fetchFt4Decode(std::vector<cwslg_ft4_msg> &out, int max = 1800, std::uint64_t *startEpoch = nullptr)
+    {
+        out.resize(max);
+        int n = 0;
+        const int rc = cwslg_fetch_ft4_decode(ctx_.raw(), id_, out.data(), max, &n, startEpoch);
         if (rc == CWSLG_ERR_NO_FRAME) { out.clear(); return 0; }
         check(ctx_.raw(), rc);
         out.resize(n);
