@@ -118,6 +118,16 @@ def ft4_best_set(rec):
     return int(best) if best.ndim == 0 else best.astype(np.int64)
 
 
+class OsdMsg(C.Structure):
+    _fields_ = [("bits", C.c_uint8 * 12), ("dmin", C.c_float), ("nharderr", C.c_int16), ("nskip", C.c_int16), ("crc_ok", C.c_uint8), ("how", C.c_uint8),
+                ("flip", C.c_uint8 * 2)]
+
+
+# numpy view of cwslg_osd_msg (24 bytes)
+OSD_MSG_DTYPE = np.dtype([("bits", np.uint8, 12), ("dmin", np.float32), ("nharderr", np.int16), ("nskip", np.int16), ("crc_ok", np.uint8), ("how", np.uint8),
+                          ("flip", np.uint8, 2)])
+
+
 class Ft4Soft(C.Structure):
     _fields_ = [("llr", (C.c_float * 174) * 3), ("sigma", C.c_float * 3), ("nsync", C.c_int32), ("nqual", C.c_int32), ("pad_", C.c_int32)]
 
@@ -163,7 +173,8 @@ ABI_SYMBOLS = [
     "cwslg_synchronize", "cwslg_fetch_frame", "cwslg_fetch_slot", "cwslg_write_wav", "cwslg_fetch_audio_f32", "cwslg_frame_device_ptrs",
     "cwslg_enable_sync", "cwslg_set_candidate_order", "cwslg_fetch_candidates", "cwslg_set_ft4_syncmin", "cwslg_enable_ft4_coherent", "cwslg_fetch_ft4_sync",
     "cwslg_enable_ft8_softbits", "cwslg_fetch_ft8_softbits", "cwslg_enable_ft4_softbits", "cwslg_fetch_ft4_softbits", "cwslg_sync_debug_fetch", "cwslg_get_stats", "cwslg_reset_stats",
-    "cwslg_set_ldpc_code", "cwslg_enable_ft8_decode", "cwslg_fetch_ft8_decode", "cwslg_ldpc_decode", "cwslg_enable_ft4_decode", "cwslg_fetch_ft4_decode",
+    "cwslg_set_ldpc_code", "cwslg_enable_ft8_decode", "cwslg_fetch_ft8_decode", "cwslg_ldpc_decode",
+    "cwslg_enable_ft8_osd", "cwslg_fetch_ft8_osd", "cwslg_osd_decode", "cwslg_enable_ft4_decode", "cwslg_fetch_ft4_decode",
     "cwslg_set_timing", "cwslg_demod_kernel_name", "cwslg_stream", "cwslg_channel_constants", "cwslg_phasor_checkpoint_stride", "cwslg_channel_phasor_checkpoints",
     "cwslg_slot_clock_next", "cwslg_pool_sizing", "cwslg_find_band", "cwslg_parse_decode_line",
     "cwslg_decoder_block_bytes", "cwslg_decoder_block_field", "cwslg_fill_decoder_block", "cwslg_decoder_route", "cwslg_decoder_command",
@@ -255,6 +266,9 @@ def load_library(build_if_missing=True):
     L.cwslg_enable_ft8_decode.argtypes = [vp, i32, i32, i32]
     L.cwslg_fetch_ft8_decode.argtypes = [vp, i32, C.POINTER(Ft8Msg), i32, C.POINTER(i32), C.POINTER(u64)]
     L.cwslg_ldpc_decode.argtypes = [vp, vp, i32, i32, vp]
+    L.cwslg_enable_ft8_osd.argtypes = [vp, i32, i32, i32]
+    L.cwslg_fetch_ft8_osd.argtypes = [vp, i32, C.POINTER(OsdMsg), i32, C.POINTER(i32), C.POINTER(u64)]
+    L.cwslg_osd_decode.argtypes = [vp, vp, i32, i32, vp]
     L.cwslg_enable_ft4_softbits.argtypes = [vp, i32]
     L.cwslg_fetch_ft4_softbits.argtypes = [vp, i32, C.POINTER(Ft4Soft), i32, C.POINTER(i32), C.POINTER(u64)]
     L.cwslg_enable_ft4_decode.argtypes = [vp, i32, i32, i32, i32]
@@ -675,6 +689,32 @@ class Context:
         llr = np.ascontiguousarray(llr, dtype=np.float32).reshape(-1, 174)
         out = np.zeros(len(llr), FT8_MSG_DTYPE)
         self._chk(self.L.cwslg_ldpc_decode(self.h, llr.ctypes.data if len(llr) else None, len(llr), int(max_iter), out.ctypes.data if len(llr) else None))
+        return out
+
+    def enable_ft8_osd(self, enable=True, order=2, min_nsync=7):
+        """Ordered-statistics decoding (order 0..2) of the FT8 candidates the decode attempted without crc_ok (cwslg_osd_msg); needs a loaded code of
+        rank 83; runs at the boundaries at which enable_ft8_softbits and enable_ft8_decode are on too."""
+        self._chk(self.L.cwslg_enable_ft8_osd(self.h, int(enable), int(order), int(min_nsync)))
+
+    def fetch_ft8_osd(self, ch, max_cand=600, with_epoch=False):
+        """-> None unless OSD records of the channel's current epoch exist, else a numpy record array (OSD_MSG_DTYPE: bits uint8[12], dmin, nharderr,
+        nskip, crc_ok, how, flip uint8[2]) whose row q belongs to entry q of fetch_candidates' list of the same epoch (with_epoch: (records, frame
+        start epoch))."""
+        buf = np.zeros(max(int(max_cand), 1), OSD_MSG_DTYPE)
+        n = C.c_int()
+        t0 = C.c_uint64()
+        rc = self.L.cwslg_fetch_ft8_osd(self.h, ch, buf.ctypes.data_as(C.POINTER(OsdMsg)), int(max_cand), C.byref(n), C.byref(t0))
+        if rc == ERR_NO_FRAME:
+            return None
+        self._chk(rc)
+        rec = buf[:n.value].copy()
+        return (rec, t0.value) if with_epoch else rec
+
+    def osd_decode(self, llr, order=2):
+        """The OSD kernel on caller-supplied metrics, llr float32[n, 174] (n >= 0), no gates; synchronous.  -> record array [n]."""
+        llr = np.ascontiguousarray(llr, dtype=np.float32).reshape(-1, 174)
+        out = np.zeros(len(llr), OSD_MSG_DTYPE)
+        self._chk(self.L.cwslg_osd_decode(self.h, llr.ctypes.data if len(llr) else None, len(llr), int(order), out.ctypes.data if len(llr) else None))
         return out
 
     def enable_ft4_softbits(self, enable=True):

@@ -48,6 +48,7 @@
 #include "ft4sync_kernels.hpp"
 #include "ft8soft_kernels.hpp"
 #include "ldpc_kernels.hpp"
+#include "osd_kernels.hpp"
 #include "ft4soft_kernels.hpp"
 #include "longsync_kernels.hpp"
 
@@ -204,6 +205,7 @@ struct Channel {
     uint64_t cand_t0 = 0;              // start epoch of the frame the candidate lists on the device were computed from (0: none yet)
     uint64_t soft_t0 = 0;              // ... the FT8 soft-bit records were computed from (cwslg_enable_ft8_softbits; 0: none)
     uint64_t soft4_t0 = 0;             // ... the FT4 soft-bit records were computed from (cwslg_enable_ft4_softbits; 0: none)
+    uint64_t osd_t0 = 0;               // ... the FT8 OSD records were computed from (cwslg_enable_ft8_osd; 0: none)
     uint64_t msg_t0 = 0;               // ... the FT8 decode records were computed from (cwslg_enable_ft8_decode; 0: none)
     uint64_t msg4_t0 = 0;              // ... the FT4 decode records were computed from (cwslg_enable_ft4_decode; 0: none)
     SyncChannelBuffers syncbuf;

@@ -104,4 +104,131 @@ inline int ldpc_derive(const uint8_t *nm, LdpcTables *out)
     return 0;
 }
 
+// ---- ordered-statistics decoding (cwslg_osd_msg in include/cwsl_gpu.h; tests/osd_ref.py restates it) ----------------------------------------------
+// A generator of the code: 91 rows of 174 bits, 6 dwords per row (codeword bit t at row[t >> 5] bit t & 31; bits 174..191 are 0) -- one 2184-byte
+// device block.  Which basis of the null space it is does not matter to the result (the most reliable basis is reduced from whatever it starts with).
+constexpr int OSD_GW = 6, OSD_NPAIR = LDPC_K * (LDPC_K - 1) / 2;
+struct OsdGen { uint32_t row[LDPC_K][OSD_GW]; };
+static_assert(sizeof(OsdGen) == 2184, "generator block");
+struct OsdRec { uint8_t bits[12]; float dmin; int16_t nharderr, nskip; uint8_t crc_ok, how, flip[2]; };    // = cwslg_osd_msg
+static_assert(sizeof(OsdRec) == 24, "cwslg_osd_msg is 24 bytes");
+
+// Rank of H over GF(2), and -- when it is 83 and gen != nullptr -- the generator whose row k carries free column f_k (ascending) alone among the
+// free columns: bit f_k, and at pivot column c_r the entry of reduced row r in column f_k.
+inline int ldpc_generator(const LdpcTables &t, OsdGen *gen)
+{
+    uint32_t h[LDPC_M][OSD_GW];
+    memset(h, 0, sizeof(h));
+    for (int m = 0; m < LDPC_M; ++m)
+        for (int e = 0; e < LDPC_ROWMAX; ++e)
+            if (t.rowbit[m][e] != LDPC_ABSENT) h[m][t.rowbit[m][e] >> 5] ^= 1u << (t.rowbit[m][e] & 31);
+    int pivcol[LDPC_M], rank = 0;
+    bool is_piv[LDPC_N] = {false};
+    for (int c = 0; c < LDPC_N && rank < LDPC_M; ++c) {
+        int r = rank;
+        while (r < LDPC_M && !((h[r][c >> 5] >> (c & 31)) & 1u)) ++r;
+        if (r == LDPC_M) continue;
+        for (int w = 0; w < OSD_GW; ++w) { const uint32_t x = h[r][w]; h[r][w] = h[rank][w]; h[rank][w] = x; }
+        for (int i = 0; i < LDPC_M; ++i)
+            if (i != rank && ((h[i][c >> 5] >> (c & 31)) & 1u))
+                for (int w = 0; w < OSD_GW; ++w) h[i][w] ^= h[rank][w];
+        pivcol[rank++] = c;
+        is_piv[c] = true;
+    }
+    if (rank != LDPC_M || !gen) return rank;
+    memset(gen, 0, sizeof(*gen));
+    int k = 0;
+    for (int f = 0; f < LDPC_N; ++f) {
+        if (is_piv[f]) continue;
+        gen->row[k][f >> 5] |= 1u << (f & 31);
+        for (int r = 0; r < LDPC_M; ++r)
+            if ((h[r][f >> 5] >> (f & 31)) & 1u) gen->row[k][pivcol[r] >> 5] |= 1u << (pivcol[r] & 31);
+        ++k;
+    }
+    return rank;
+}
+
+// d(c) of the contract: float32 adds of a[t] over the set bits of the error pattern, ascending t
+inline float osd_distance(const uint32_t *e, const float *a)
+{
+    float d = 0.0f;
+    for (int t = 0; t < LDPC_N; ++t)
+        if ((e[t >> 5] >> (t & 31)) & 1u) d = d + a[t];
+    return d;
+}
+
+// The whole contract on the host, one set of metrics: what osd_decode_kernel computes (tests/osd_host_check.cpp prints it).
+inline void osd_host(const OsdGen &gen, const float *llr, int order, OsdRec *out)
+{
+    memset(out, 0, sizeof(*out));
+    out->nharderr = out->nskip = -1;
+    out->how = out->flip[0] = out->flip[1] = 0xff;
+    float a[LDPC_N];
+    uint32_t hard[OSD_GW] = {0};
+    for (int t = 0; t < LDPC_N; ++t) {
+        a[t] = fabsf(llr[t]);
+        if (!(a[t] < INFINITY)) return;                        // not attempted
+        if (llr[t] > 0.0f) hard[t >> 5] |= 1u << (t & 31);
+    }
+    int perm[LDPC_N];
+    for (int t = 0; t < LDPC_N; ++t) {
+        int r = 0;
+        for (int u = 0; u < LDPC_N; ++u) r += (a[u] > a[t]) || (a[u] == a[t] && u < t);
+        perm[r] = t;
+    }
+    OsdGen g = gen;
+    int rowof[LDPC_K], pos[LDPC_K], npiv = 0, k = 0;           // rowof[i]: the row that became g_i; pos[i] = p_i
+    bool used[LDPC_K] = {false};
+    uint32_t c0[OSD_GW] = {0};
+    for (; k < LDPC_N && npiv < LDPC_K; ++k) {
+        const int t = perm[k], w = t >> 5;
+        const uint32_t bm = 1u << (t & 31);
+        int r = 0;
+        while (r < LDPC_K && (used[r] || !(g.row[r][w] & bm))) ++r;
+        if (r == LDPC_K) continue;
+        for (int i = 0; i < LDPC_K; ++i)
+            if (i != r && (g.row[i][w] & bm))
+                for (int x = 0; x < OSD_GW; ++x) g.row[i][x] ^= g.row[r][x];
+        used[r] = true;
+        pos[npiv] = t;
+        rowof[npiv++] = r;
+    }
+    if (npiv != LDPC_K) return;
+    for (int i = 0; i < LDPC_K; ++i)
+        if ((hard[pos[i] >> 5] >> (pos[i] & 31)) & 1u)
+            for (int x = 0; x < OSD_GW; ++x) c0[x] ^= g.row[rowof[i]][x];
+    uint32_t e[OSD_GW], best[OSD_GW];
+    for (int x = 0; x < OSD_GW; ++x) best[x] = e[x] = c0[x] ^ hard[x];
+    float dmin = osd_distance(e, a);
+    int how = 0, fi = 0xff, fj = 0xff;
+    if (order >= 1)
+        for (int i = 0; i < LDPC_K; ++i) {
+            uint32_t c[OSD_GW];
+            for (int x = 0; x < OSD_GW; ++x) c[x] = e[x] ^ g.row[rowof[i]][x];
+            const float d = osd_distance(c, a);
+            if (d < dmin) { dmin = d; how = 1; fi = i; fj = 0xff; memcpy(best, c, sizeof(c)); }
+        }
+    if (order >= 2)
+        for (int i = 0; i < LDPC_K; ++i)
+            for (int j = i + 1; j < LDPC_K; ++j) {
+                uint32_t c[OSD_GW];
+                for (int x = 0; x < OSD_GW; ++x) c[x] = e[x] ^ g.row[rowof[i]][x] ^ g.row[rowof[j]][x];
+                const float d = osd_distance(c, a);
+                if (d < dmin) { dmin = d; how = 2; fi = i; fj = j; memcpy(best, c, sizeof(c)); }
+            }
+    int nh = 0;
+    for (int t = 0; t < LDPC_N; ++t) nh += (best[t >> 5] >> (t & 31)) & 1u;
+    uint32_t cw[OSD_GW];
+    for (int x = 0; x < OSD_GW; ++x) cw[x] = best[x] ^ hard[x];
+    const uint64_t lo = cw[0] | ((uint64_t)cw[1] << 32), hi = (cw[2] | ((uint64_t)cw[3] << 32)) & ((1ull << (LDPC_K - 64)) - 1);
+    for (int t = 0; t < LDPC_K; ++t) if (ldpc_cw_bit(lo, hi, t)) out->bits[t >> 3] |= (uint8_t)(0x80 >> (t & 7));
+    out->dmin = dmin;
+    out->nharderr = (int16_t)nh;
+    out->nskip = (int16_t)(k - LDPC_K);
+    out->crc_ok = ldpc_crc14(lo, hi) == ldpc_crc_field(lo, hi);
+    out->how = (uint8_t)how;
+    out->flip[0] = (uint8_t)fi;
+    out->flip[1] = (uint8_t)fj;
+}
+
 } // namespace cwslg

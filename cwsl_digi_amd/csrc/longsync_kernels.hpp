@@ -342,9 +342,8 @@ __device__ __forceinline__ void load_i16x8(const CWSLG_GLOBAL int16_t *frame, in
 // 128 frames) -- and dealt out to the 16 packed sequences through LDS (index n + n/32: the stride-32 reads of the deal fall on 32
 // different banks).  wsprd's sample n is frame[n - 1] (wspr_sample above), so the aligned chunk frame[N0 + 8 c ...] lands on local samples
 // 8 c + 1 ... 8 c + 8; local sample 0 is the last element of the previous workgroup's range (the header word for the first).
-__global__ __launch_bounds__(256) void wspr_pack_kernel(const LongWork *__restrict__ works)
+__device__ __forceinline__ void wspr_pack(const LongWork *__restrict__ works, float *s_x)
 {
-    __shared__ float s_x[WSPR_R * 256 + 256];
     const LongWork *w = works + blockIdx.y;
     const CWSLG_GLOBAL int16_t *frame = as_global(w->frame);
     const int frame_len = w->frame_len;
@@ -615,9 +614,8 @@ __global__ __launch_bounds__(256) void wspr_coarse_kernel(const LongWork *__rest
 // ---------------------------------------------------------------------------------------------
 // FST4W-120.  z[p][b] = x[45 b + p] + i x[45 b + p + 22]; p = 22 carries a = 44 alone.  grid (M / 256, channels): 256 consecutive b =
 // 11520 consecutive samples read once, dealt out through LDS (stride 45 is odd: conflict-free).
-__global__ __launch_bounds__(256) void fst4w_pack_kernel(const LongWork *__restrict__ works)
+__device__ __forceinline__ void fst4w_pack(const LongWork *__restrict__ works, float *s_x)
 {
-    __shared__ float s_x[F4W_R * 256];
     const LongWork *w = works + blockIdx.y;
     const CWSLG_GLOBAL int16_t *frame = as_global(w->frame);
     const int lim = min(w->frame_len, F4W_NMAX);              // samples at and beyond either bound read as zero
@@ -637,6 +635,16 @@ __global__ __launch_bounds__(256) void fst4w_pack_kernel(const LongWork *__restr
         const float x2 = (p < 22) ? s_x[F4W_R * tid + p + 22] : 0.0f;
         z[(size_t)p * F4W_M + b0 + tid] = v2f{x1, x2};
     }
+}
+
+// The two pack passes as ONE kernel (the product library's inventory is capped): `fst4w` selects the body, wave-uniformly; each body is the
+// instruction stream it was as a kernel of its own and takes the LDS it took (dynamic: LONG_PACK_LDS_WSPR / _FST4W bytes at the launch).
+constexpr unsigned LONG_PACK_LDS_WSPR = (WSPR_R * 256 + 256) * sizeof(float), LONG_PACK_LDS_FST4W = F4W_R * 256 * sizeof(float);
+__global__ __launch_bounds__(256) void long_pack_kernel(const LongWork *__restrict__ works, int fst4w)
+{
+    extern __shared__ float s_pack[];
+    if (fst4w) fst4w_pack(works, s_pack);
+    else wspr_pack(works, s_pack);
 }
 
 // c_bigfft(k) for k = jlo .. jlo + nband - 1.  grid (125, channels), 256 threads: the workgroup owns the residue c = k mod 125 and

@@ -168,12 +168,14 @@ int sync_ensure_channel(cwslg_ctx *c, Channel &ch)
     const int want_bins = ch.sync_ft4 ? FT4_ROW : cfg.nbins;
     const bool want_soft = cfg.ft8_soft && ch.sync_ft8;      // the soft-bit records exist only while the feature is on (a later enable reallocates)
     const bool want_msg = want_soft && cfg.ft8_decode;       // ... and so do the decode records
+    const bool want_osd = want_msg && cfg.ft8_osd;           // ... and the OSD records
     if (b.d_block && b.nbins == want_bins && b.max_cand == cfg.max_cand && b.ft4 == ch.sync_ft4 && (b.d_soft != nullptr) == want_soft &&
-        (b.d_msg != nullptr) == want_msg)
+        (b.d_msg != nullptr) == want_msg && (b.d_osd != nullptr) == want_osd)
         return CWSLG_OK;
     sync_free_channel(b);
     ch.soft_t0 = 0;
     ch.msg_t0 = 0;
+    ch.osd_t0 = 0;
     ch.soft4_t0 = 0;
     ch.msg4_t0 = 0;
     const size_t sp = ((size_t)(ch.sync_ft4 ? FT4_NHSYM : FT8_NHSYM) * want_bins * sizeof(float) + 255) & ~size_t(255);
@@ -181,7 +183,9 @@ int sync_ensure_channel(cwslg_ctx *c, Channel &ch)
     const size_t cand = ((size_t)cfg.max_cand * sizeof(SyncChannelBuffers::Cand) + 255) & ~size_t(255);
     const size_t soft = want_soft ? (size_t)cfg.max_cand * sizeof(Ft8SoftRec) : 0;
     const size_t msg = want_msg ? (size_t)cfg.max_cand * sizeof(Ft8MsgRec) : 0;
-    HIPCHK(c, hipMalloc((void **)&b.d_block, sp + 4 * vec + cand + 256 + soft + msg));
+    const size_t msg_pad = want_osd ? (msg + 7) & ~size_t(7) : msg;      // (the OSD records hold a float: keep them 8-byte aligned)
+    const size_t osd = want_osd ? (size_t)cfg.max_cand * sizeof(OsdRec) : 0;
+    HIPCHK(c, hipMalloc((void **)&b.d_block, sp + 4 * vec + cand + 256 + soft + msg_pad + osd));
     char *p = b.d_block;
     b.d_spectra = (float *)p; p += sp;
     b.d_red = (float *)p; p += vec;
@@ -191,7 +195,8 @@ int sync_ensure_channel(cwslg_ctx *c, Channel &ch)
     b.d_cand = (SyncChannelBuffers::Cand *)p; p += cand;
     b.d_ncand = (int *)p; p += 256;
     if (want_soft) { b.d_soft = (Ft8SoftRec *)p; p += soft; }
-    if (want_msg) b.d_msg = (Ft8MsgRec *)p;
+    if (want_msg) { b.d_msg = (Ft8MsgRec *)p; p += msg_pad; }
+    if (want_osd) b.d_osd = (OsdRec *)p;
     b.nbins = want_bins;
     b.max_cand = cfg.max_cand;
     b.ft4 = ch.sync_ft4;
@@ -224,6 +229,21 @@ void ldpc_launch_ft4(hipStream_t st, const void *tables, const Ft4Work *works4, 
                        max_iter, min_nsync, (const LdpcTables *)tables, works4, soft4, msg4, min_nqual);
 }
 
+// osd_decode_kernel's two addressing modes
+//   FT8 chain: one wave per candidate of n_chan channels, behind the decode records it gates on
+void osd_launch_ft8(hipStream_t st, const void *gen, const SyncWork *works, Ft8SoftRec *const *soft, Ft8MsgRec *const *msg, OsdRec *const *osd, size_t n_chan,
+                    int max_cand, int order, int min_nsync)
+{
+    hipLaunchKernelGGL(osd_decode_kernel, dim3((unsigned)((max_cand + OSD_WAVES - 1) / OSD_WAVES), (unsigned)n_chan), dim3(64 * OSD_WAVES), 0, st, works, soft, msg, osd,
+                       (const float *)nullptr, (OsdRec *)nullptr, 0, max_cand, order, min_nsync, (const OsdGen *)gen);
+}
+//   flat: n sets of 174 metrics, no gate
+void osd_launch_flat(hipStream_t st, const void *gen, const float *llr, OsdRec *out, int n, int order)
+{
+    hipLaunchKernelGGL(osd_decode_kernel, dim3((unsigned)((n + OSD_WAVES - 1) / OSD_WAVES), 1), dim3(64 * OSD_WAVES), 0, st, (const SyncWork *)nullptr,
+                       (Ft8SoftRec *const *)nullptr, (Ft8MsgRec *const *)nullptr, (OsdRec *const *)nullptr, llr, out, n, 0, order, 0, (const OsdGen *)gen);
+}
+
 // Run the sync stage on the frames finalised by this boundary: FT8 channels through the Costas search, FT4
 // channels through getcandidates4's spectral-peak search.  Other modes have no sync stage.
 int sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
@@ -237,6 +257,7 @@ int sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
     std::vector<Ft4MsgRec *> msg4;                            // cwslg_enable_ft4_decode (with the coherent stage and soft bits on): one record array per FT4 channel, in works4c's order
     std::vector<Ft8SoftRec *> soft8;                          // cwslg_enable_ft8_softbits: one record array per FT8 channel, in works8's order
     std::vector<Ft8MsgRec *> msg8;                            // cwslg_enable_ft8_decode (with soft bits on): one record array per FT8 channel, in works8's order
+    std::vector<OsdRec *> osd8;                               // cwslg_enable_ft8_osd (with soft bits and decode on): one record array per FT8 channel, in works8's order
     for (int id : emitted) {
         Channel &ch = c->chans[id];
         if (!ch.sync_ft8 && !ch.sync_ft4) continue;
@@ -257,6 +278,10 @@ int sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
             if (cfg.ft8_decode) {
                 msg8.push_back(ch.syncbuf.d_msg);
                 ch.msg_t0 = ch.frame_t0;                      // ... and the decode records, under the same rule
+                if (cfg.ft8_osd) {
+                    osd8.push_back(ch.syncbuf.d_osd);
+                    ch.osd_t0 = ch.frame_t0;                  // ... and the OSD records
+                }
             }
         }
         if (ch.sync_ft4 && cfg.ft4_coherent) {
@@ -284,13 +309,14 @@ int sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
     if (works8.empty() && works4.empty()) return CWSLG_OK;
     const size_t n8 = works8.size(), n4 = works4.size();
     // the soft-bit launch's record pointers ride behind the descriptors in the same buffer (nothing is added while the feature is off)
-    const size_t wb_bytes = (n8 + n4) * sizeof(SyncWork) + soft8.size() * sizeof(Ft8SoftRec *) + msg8.size() * sizeof(Ft8MsgRec *);
+    const size_t wb_bytes = (n8 + n4) * sizeof(SyncWork) + soft8.size() * sizeof(Ft8SoftRec *) + msg8.size() * sizeof(Ft8MsgRec *) + osd8.size() * sizeof(OsdRec *);
     WorkBuf *wb = acquire_workbuf(c, wb_bytes);
     if (!wb) return fail(c, CWSLG_ERR_NOMEM, "work buffer allocation failed");
     if (n8) std::memcpy(wb->h, works8.data(), n8 * sizeof(SyncWork));
     if (n4) std::memcpy((SyncWork *)wb->h + n8, works4.data(), n4 * sizeof(SyncWork));
     if (!soft8.empty()) std::memcpy((SyncWork *)wb->h + n8 + n4, soft8.data(), soft8.size() * sizeof(Ft8SoftRec *));
     if (!msg8.empty()) std::memcpy((Ft8SoftRec **)((SyncWork *)wb->h + n8 + n4) + soft8.size(), msg8.data(), msg8.size() * sizeof(Ft8MsgRec *));
+    if (!osd8.empty()) std::memcpy((Ft8SoftRec **)((SyncWork *)wb->h + n8 + n4) + soft8.size() + msg8.size(), osd8.data(), osd8.size() * sizeof(OsdRec *));
     HIPCHK(c, upload_workbuf(c, wb, wb_bytes));
     // one wave per candidate behind whichever search form wrote d_cand / d_ncand (the count is read on the device); its time is part of the
     // stage's span (stats.sync_ms), not of the search's own
@@ -303,6 +329,11 @@ int sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
         Ft8SoftRec *const *dsoft = (Ft8SoftRec *const *)((const SyncWork *)wb->d + n8 + n4);
         ldpc_launch_ft8(st, c->sync_shared.d_ldpc, (const SyncWork *)wb->d, dsoft, (Ft8MsgRec *const *)(dsoft + n8), n8, cfg.max_cand, cfg.ldpc_max_iter,
                         cfg.ldpc_min_nsync);
+        c->stats.sync_launches++;
+        // OSD: one wave per candidate behind the decode records it gates on; counted as a launch of its own
+        if (osd8.empty()) return;
+        osd_launch_ft8(st, c->sync_shared.d_osdgen, (const SyncWork *)wb->d, dsoft, (Ft8MsgRec *const *)(dsoft + n8), (OsdRec *const *)(dsoft + 2 * n8), n8, cfg.max_cand,
+                       cfg.osd_order, cfg.osd_min_nsync);
         c->stats.sync_launches++;
     };
     WorkBuf *wb4 = nullptr;
@@ -515,6 +546,7 @@ int cwslg_enable_sync(cwslg_ctx *c, int enable, float syncmin, int max_cand, int
         cfg.ft8_soft = c->sync_cfg.ft8_soft;
         cfg.ft4_soft = c->sync_cfg.ft4_soft;
         cfg.ft8_decode = c->sync_cfg.ft8_decode; cfg.ldpc_max_iter = c->sync_cfg.ldpc_max_iter; cfg.ldpc_min_nsync = c->sync_cfg.ldpc_min_nsync;
+        cfg.ft8_osd = c->sync_cfg.ft8_osd; cfg.osd_order = c->sync_cfg.osd_order; cfg.osd_min_nsync = c->sync_cfg.osd_min_nsync;
         cfg.ft4_decode = c->sync_cfg.ft4_decode; cfg.ldpc4_max_iter = c->sync_cfg.ldpc4_max_iter; cfg.ldpc4_min_nsync = c->sync_cfg.ldpc4_min_nsync;
         cfg.ldpc4_min_nqual = c->sync_cfg.ldpc4_min_nqual;
         if (cfg.ft8_soft) cfg.nbins = (cfg.ib + 15 + 31) / 32 * 32;   // soft bits on: tone 7 of bin ib (ib + 14) lies inside the row
@@ -631,6 +663,19 @@ int cwslg_fetch_ft8_softbits(cwslg_ctx *c, int ch_id, cwslg_ft8_soft *dst, int m
     return CWSLG_OK;
 }
 
+// The generator's device block exists from the first use of OSD on (while OSD has never been used a context holds no byte of it).
+hipError_t osd_upload_gen(cwslg_ctx *c)
+{
+    SyncShared &s = c->sync_shared;
+    hipError_t e = hipSuccess;
+    if (!s.d_osdgen && (e = hipMalloc(&s.d_osdgen, sizeof(OsdGen))) != hipSuccess) return e;
+    if (!s.osd_dirty) return hipSuccess;
+    if ((e = sync_streams(c)) != hipSuccess) return e;
+    if ((e = hipMemcpy(s.d_osdgen, s.osd_gen, sizeof(OsdGen), hipMemcpyHostToDevice)) != hipSuccess) return e;
+    s.osd_dirty = false;
+    return hipSuccess;
+}
+
 // FT8 decode (ldpc_kernels.hpp).  The parity-check table is the caller's data: validated and turned into the kernel's tables on the host
 // (ldpc_host.hpp), uploaded with the context's streams drained -- a new table applies to every launch queued after the call.
 int cwslg_set_ldpc_code(cwslg_ctx *c, const uint8_t *nm)
@@ -644,11 +689,24 @@ int cwslg_set_ldpc_code(cwslg_ctx *c, const uint8_t *nm)
                                              "a position that does not occur exactly three times"};
         return fail(c, CWSLG_ERR_ARG, "LDPC table rejected: %s", reason[why]);
     }
+    // OSD's generator of the same code (osd_kernels.hpp); a table whose H has rank below 83 is still a code the BP decode takes, but OSD cannot
+    // run on it: loading one switches OSD off
+    OsdGen gen;
+    const bool full_rank = ldpc_generator(t, &gen) == LDPC_M;
     hipSetDevice(c->device);
     if (!c->sync_shared.d_ldpc) HIPCHK(c, hipMalloc(&c->sync_shared.d_ldpc, sizeof(LdpcTables)));
     HIPCHK(c, sync_streams(c));                                // no queued decode launch may still read the old tables
     HIPCHK(c, hipMemcpy(c->sync_shared.d_ldpc, &t, sizeof(LdpcTables), hipMemcpyHostToDevice));
     c->sync_shared.ldpc_loaded = true;
+    c->sync_shared.osd_ready = false;
+    if (full_rank) {
+        static_assert(sizeof(c->sync_shared.osd_gen) == sizeof(OsdGen), "generator block");
+        std::memcpy(c->sync_shared.osd_gen, &gen, sizeof(OsdGen));
+        c->sync_shared.osd_ready = c->sync_shared.osd_dirty = true;
+        if (c->sync_shared.d_osdgen) HIPCHK(c, osd_upload_gen(c));      // (the streams are drained: no queued OSD launch still reads the old block)
+    } else {
+        c->sync_cfg.ft8_osd = false;
+    }
     return CWSLG_OK;
 }
 
@@ -723,6 +781,83 @@ int cwslg_ldpc_decode(cwslg_ctx *c, const float *llr, int n, int max_iter, cwslg
     (void)hipFree(d);
     if (e == hipSuccess) e = es;
     if (e != hipSuccess) return fail(c, CWSLG_ERR_HIP, "cwslg_ldpc_decode failed: %s", hipGetErrorString(e));
+    return CWSLG_OK;
+}
+
+// FT8 OSD (osd_kernels.hpp): one launch behind the decode launch, on the candidates it attempted without crc_ok.
+int cwslg_enable_ft8_osd(cwslg_ctx *c, int enable, int order, int min_nsync)
+{
+    if (!c) return CWSLG_ERR_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    SyncConfig &cfg = c->sync_cfg;
+    if (!enable) { cfg.ft8_osd = false; return CWSLG_OK; }
+    if (order < 0 || order > 2 || min_nsync < 0 || min_nsync > 22) return fail(c, CWSLG_ERR_ARG, "FT8 OSD parameters out of range");
+    if (!c->sync_shared.osd_ready) return fail(c, CWSLG_ERR_ARG, "FT8 OSD needs a parity-check table of rank 83 (cwslg_set_ldpc_code)");
+    hipSetDevice(c->device);
+    HIPCHK(c, osd_upload_gen(c));
+    cfg.ft8_osd = true; cfg.osd_order = order; cfg.osd_min_nsync = min_nsync;
+    return CWSLG_OK;
+}
+
+// Handed out like the decode records, and only together with them: OSD, decode and soft-bit records, list and frame of ONE epoch.
+int cwslg_fetch_ft8_osd(cwslg_ctx *c, int ch_id, cwslg_osd_msg *dst, int max, int *n, uint64_t *start_epoch)
+{
+    if (!c || !n || (max > 0 && !dst)) return CWSLG_ERR_ARG;
+    *n = 0;
+    const OsdRec *src = nullptr;
+    const int *cnt_src = nullptr;
+    int lim = 0;
+    ResultFetch rf;
+    {
+        std::lock_guard<std::mutex> g(c->mu);
+        if (ch_id < 0 || ch_id >= (int)c->chans.size() || !c->chans[ch_id].open) return fail(c, CWSLG_ERR_ARG, "bad channel id");
+        Channel &ch = c->chans[ch_id];
+        if (!ch.sync_ft8) return fail(c, CWSLG_ERR_MODE, "OSD records exist for FT8 channels only (mode %s)", ch.mode.c_str());
+        if (!ch.have_frame || !ch.syncbuf.d_block || !ch.syncbuf.d_osd || !ch.osd_t0 || ch.osd_t0 != ch.frame_t0 || ch.osd_t0 != ch.cand_t0 ||
+            ch.osd_t0 != ch.soft_t0 || ch.osd_t0 != ch.msg_t0)
+            return CWSLG_ERR_NO_FRAME;
+        hipSetDevice(c->device);
+        if (start_epoch) *start_epoch = ch.osd_t0;
+        src = ch.syncbuf.d_osd; cnt_src = ch.syncbuf.d_ncand; lim = std::min(std::max(max, 0), ch.syncbuf.max_cand);
+        int rc = begin_result_fetch(c, ch, rf);
+        if (rc) return rc;
+    }
+    static_assert(sizeof(cwslg_osd_msg) == sizeof(OsdRec), "record layout");
+    int cnt = 0;
+    std::vector<OsdRec> tmp((size_t)lim);
+    HIPCHK(c, hipStreamWaitEvent(rf.fs, rf.ev, 0));
+    HIPCHK(c, hipMemcpyAsync(&cnt, cnt_src, sizeof(int), hipMemcpyDeviceToHost, rf.fs));
+    if (lim > 0) HIPCHK(c, hipMemcpyAsync(tmp.data(), src, (size_t)lim * sizeof(OsdRec), hipMemcpyDeviceToHost, rf.fs));
+    HIPCHK(c, hipStreamSynchronize(rf.fs));
+    cnt = std::max(0, std::min(cnt, lim));
+    if (cnt > 0) std::memcpy(dst, tmp.data(), (size_t)cnt * sizeof(OsdRec));
+    *n = cnt;
+    return CWSLG_OK;
+}
+
+// The same kernel on n sets of 174 metrics from host memory, no gates; synchronous (temporary device buffers, the context's stream).
+int cwslg_osd_decode(cwslg_ctx *c, const float *llr, int n, int order, cwslg_osd_msg *out)
+{
+    if (!c || n < 0 || (n > 0 && (!llr || !out))) return CWSLG_ERR_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    if (order < 0 || order > 2) return fail(c, CWSLG_ERR_ARG, "order out of range (0..2)");
+    if (!c->sync_shared.osd_ready) return fail(c, CWSLG_ERR_ARG, "no parity-check table of rank 83 loaded (cwslg_set_ldpc_code)");
+    if (n == 0) return CWSLG_OK;
+    hipSetDevice(c->device);
+    HIPCHK(c, osd_upload_gen(c));
+    const size_t in_bytes = (size_t)n * LDPC_N * sizeof(float), out_bytes = (size_t)n * sizeof(OsdRec);
+    char *d = nullptr;
+    HIPCHK(c, hipMalloc((void **)&d, in_bytes + out_bytes));      // (in_bytes is a multiple of 8: the records behind it are aligned)
+    hipError_t e = hipMemcpyAsync(d, llr, in_bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        osd_launch_flat(c->stream, c->sync_shared.d_osdgen, (const float *)d, (OsdRec *)(d + in_bytes), n, order);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d + in_bytes, out_bytes, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    (void)hipFree(d);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(c, CWSLG_ERR_HIP, "cwslg_osd_decode failed: %s", hipGetErrorString(e));
     return CWSLG_OK;
 }
 

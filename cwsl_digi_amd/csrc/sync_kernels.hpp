@@ -49,6 +49,8 @@ struct SyncConfig {
     int ldpc_max_iter = 30, ldpc_min_nsync = 7;
     bool ft4_decode = false;              // cwslg_enable_ft4_decode: the same decode on the three metric sets of every FT4 soft-bit record; runs only while ft4_coherent and ft4_soft are on too
     int ldpc4_max_iter = 30, ldpc4_min_nsync = 8, ldpc4_min_nqual = 20;
+    bool ft8_osd = false;                 // cwslg_enable_ft8_osd: ordered-statistics decoding of the candidates the FT8 decode attempted without crc_ok (osd_kernels.hpp); runs only while ft8_soft and ft8_decode are on too
+    int osd_order = 2, osd_min_nsync = 7;
 };
 
 struct SyncTables {                       // device pointers: W_NZ, W_128, 0.5 W_2NZ twiddles, optional window
@@ -66,6 +68,10 @@ struct SyncShared {
     const float2 *ft4_w32 = nullptr;      // inside d_ft4c: [32] (cos, +sin) of 2 pi p / 32, ft4_softbits_kernel's symbol spectra (ft4soft_kernels.hpp)
     void *d_ldpc = nullptr;               // LdpcTables (ldpc_host.hpp) derived from the caller's parity-check table; allocated by the first cwslg_set_ldpc_code
     bool ldpc_loaded = false;
+    uint32_t osd_gen[91 * 6] = {};        // OsdGen (ldpc_host.hpp): a generator of the loaded code, derived with the tables while rank H = 83
+    void *d_osdgen = nullptr;             // its device copy: allocated by the first cwslg_enable_ft8_osd / cwslg_osd_decode, replaced by every later cwslg_set_ldpc_code
+    bool osd_ready = false;               // the loaded code has rank 83: OSD may be enabled
+    bool osd_dirty = false;               // osd_gen is newer than the device copy
 };
 
 struct SyncChannelBuffers {
@@ -77,6 +83,7 @@ struct SyncChannelBuffers {
     int *d_ncand = nullptr;
     struct Ft8SoftRec *d_soft = nullptr;  // [max_cand], FT8 channels while cwslg_enable_ft8_softbits is on (part of d_block)
     struct Ft8MsgRec *d_msg = nullptr;    // [max_cand], FT8 channels while soft bits AND cwslg_enable_ft8_decode are on (part of d_block, behind d_soft)
+    struct OsdRec *d_osd = nullptr;       // [max_cand], FT8 channels while soft bits, decode AND cwslg_enable_ft8_osd are on (part of d_block, behind d_msg)
     int nbins = 0, max_cand = 0;
     bool ft4 = false;                     // FT4 layout: spectra [122][FT4_ROW]; red = normalised savsm, red2 = sbase
     // FT4 coherent sync (ft4sync_kernels.hpp): frame spectrum, its stage-A scratch, refined records
@@ -115,6 +122,7 @@ inline void sync_free_shared(SyncShared &s)
     if (s.d_ft4c) (void)hipFree(s.d_ft4c);
     if (s.d_ft4c_win) (void)hipFree(s.d_ft4c_win);
     if (s.d_ldpc) (void)hipFree(s.d_ldpc);
+    if (s.d_osdgen) (void)hipFree(s.d_osdgen);
     s = SyncShared();
 }
 

@@ -420,7 +420,7 @@ int cwslg_fetch_ft8_softbits(cwslg_ctx *ctx, int ch_id, cwslg_ft8_soft *dst, int
 /* FT8 decode (row a13; PARITY UNPINNED): flooding sum-product decoding of the LDPC(174,91) code on the 174 metrics of every cwslg_ft8_soft record,
  * then the CRC-14 -- the first consumer of those metrics, on the device: per candidate 91 bits, "is a codeword", "CRC matches" and an iteration
  * count (20 bytes) instead of 704 bytes over the link and belief propagation on the host.  Structured like upstream bpdecode174_91.  Out of scope:
- * ordered-statistics decoding, a-priori passes, signal subtraction, unpacking the 77 bits into text, de-duplication (neighbouring candidates of
+ * ordered-statistics decoding (a stage of its own: FT8 OSD below), a-priori passes, signal subtraction, unpacking the 77 bits into text, de-duplication (neighbouring candidates of
  * one transmission repeat one message).  Off by default; while it is off nothing changes (launches, buffers, upload bytes, lists, records).
  *   The code is DATA THE CALLER LOADS: the WSJT-X source is not part of this repository and its parity-check table is not reproduced here.
  *       cwslg_set_ldpc_code takes the 83 x 7 table `Nm` of the integrator's own WSJT-X tree (recalled, not checked here, as lib/ft8/ldpc_174_91_c_parity.f90), row-major: entry =
@@ -471,6 +471,49 @@ int cwslg_set_ldpc_code(cwslg_ctx *ctx, const uint8_t *nm /* [83*7] */);
 int cwslg_enable_ft8_decode(cwslg_ctx *ctx, int enable, int max_iter, int min_nsync);
 int cwslg_fetch_ft8_decode(cwslg_ctx *ctx, int ch_id, cwslg_ft8_msg *dst, int max, int *n, uint64_t *start_epoch);
 int cwslg_ldpc_decode(cwslg_ctx *ctx, const float *llr /* [n][174] */, int n, int max_iter, cwslg_ft8_msg *out);
+/* FT8 OSD (PARITY UNPINNED): ordered-statistics decoding, order 0, 1 or 2, of the candidates the decode above attempted and did not bring to
+ * crc_ok -- the last stage of the chain on the device: 24 bytes per candidate instead of a second fetch of its 704 bytes of metrics and OSD on
+ * the host.  This is the repository's OWN statement of OSD on the channel metrics; it is not upstream osd174_91, which takes reliabilities summed
+ * over BP iterations and applies its own thresholds.  False accepts under a 14-bit CRC grow with the order: dmin, nharderr and how are handed
+ * out so that the consumer can gate on them.  Off by default; while it is off nothing changes (launches, buffers, upload bytes, records).
+ *   Inputs: llr[174] (float32), the loaded code with parity check H (83 x 174) of rank 83 (K = 91), order in {0, 1, 2}.
+ *     1. a[t] = |llr[t]|, hard[t] = llr[t] > 0 (the decode record's own rule for z).  If any a[t] is not finite the record is NOT ATTEMPTED.
+ *     2. Reliability order: position t comes before u iff a[t] > a[u], or a[t] == a[u] and t < u.
+ *     3. Most reliable basis: walk the positions in that order; a position joins iff its column of a generator of the code is linearly
+ *        independent over GF(2) of the columns already taken; stop at the 91st.  p_0 .. p_90 are the taken positions in joining order, nskip the
+ *        number of positions passed over.  Both depend on the code and the order alone, not on which generator the host derived.
+ *     4. Reduced basis: the unique codewords g_i with g_i[p_j] = (i == j).
+ *     5. Order-0 word: c0 = XOR of the g_i with hard[p_i] = 1.
+ *     6. Candidates: c0 (0 flips); order >= 1: c0 ^ g_i (91 words); order == 2: c0 ^ g_i ^ g_j, i < j (4095 words).
+ *     7. Distance: d(c) = (((+0 + m_0 a[0]) + m_1 a[1]) + ...) + m_173 a[173], m_t = 1 iff c[t] != hard[t]: float32 adds in ascending t, one
+ *        operation each, nothing fused (skipping a term and adding +0 give the same bits).
+ *     8. Winner: the smallest d; ties go to fewer flips, then the smaller i, then the smaller j.
+ *   Record: bits = the winner's codeword positions 0..90, packed as cwslg_ft8_msg.bits; crc_ok by the CRC-14 rule above on the winner (always a
+ *     codeword).  A record that is not attempted has zero bits, dmin = +0, nharderr = nskip = -1, crc_ok = 0, how = flip[0] = flip[1] = 0xff.
+ * cwslg_set_ldpc_code also derives the rank of H and a generator of its null space; it accepts exactly what it accepted before, and a table
+ * whose rank is below 83 simply cannot have OSD enabled (loading one switches OSD off).  Loading a code replaces the generator for every launch
+ * queued after the call.
+ * cwslg_enable_ft8_osd(ctx, 1, order 0..2, min_nsync 0..22) returns CWSLG_ERR_ARG unless a code of rank 83 is loaded and the arguments are in
+ * range; switching it off is always allowed.  Like the decode it takes effect only while FT8 soft bits and the FT8 decode are both on at a
+ * boundary: then one launch follows the decode launch on the same stream, the candidate count read on the device, and candidate q is attempted
+ * iff its cwslg_ft8_msg was attempted (iters >= 0) and has crc_ok == 0 and its soft-bit record has nsync >= min_nsync.  That launch is counted
+ * in stats.sync_launches (three per boundary with soft bits, decode and OSD on): sync_ms / sync_launches is then A THIRD of the per-boundary
+ * time.  cwslg_fetch_ft8_osd behaves like cwslg_fetch_ft8_decode: same ticket, record q belongs to list entry q, *n = min(list length, max),
+ * CWSLG_ERR_MODE for a channel that is not FT8, CWSLG_ERR_NO_FRAME unless OSD, decode and soft-bit records, list and frame are of one epoch.
+ * cwslg_osd_decode runs the same kernel on n >= 0 caller-supplied sets of 174 metrics (host memory) with no gates, synchronously; it returns
+ * CWSLG_ERR_ARG without a loaded code of rank 83 or for an order outside 0..2.  The FT4 chain has no OSD stage yet. */
+typedef struct {
+    uint8_t bits[12];     /* the winner's codeword positions 0..90, MSB first, as cwslg_ft8_msg.bits; the last 5 bits are 0           */
+    float dmin;           /* the winner's distance d                                                                                 */
+    int16_t nharderr;     /* #{t < 174 : winner[t] != hard[t]}; -1 when not attempted                                                */
+    int16_t nskip;        /* positions passed over while the basis was chosen; -1 when not attempted                                 */
+    uint8_t crc_ok;       /* the CRC-14 of bits 0..76 equals bits 77..90                                                             */
+    uint8_t how;          /* flips of the winner, 0..2; 0xff = not attempted                                                         */
+    uint8_t flip[2];      /* i, j (joining order of the basis); 0xff where unused                                                    */
+} cwslg_osd_msg;          /* 24 bytes */
+int cwslg_enable_ft8_osd(cwslg_ctx *ctx, int enable, int order, int min_nsync);
+int cwslg_fetch_ft8_osd(cwslg_ctx *ctx, int ch_id, cwslg_osd_msg *dst, int max, int *n, uint64_t *start_epoch);
+int cwslg_osd_decode(cwslg_ctx *ctx, const float *llr /* [n][174] */, int n, int order, cwslg_osd_msg *out);
 /* FT4 soft bits (row a13; PARITY UNPINNED, restated from upstream ft4_decode's last stage before LDPC: the final ft4_downsample at the corrected
  * frequency, get_ft4_bitmetrics' three metric sets, the sync-quality counts nsync / nqual, normalizebmet, scalefac = 2.83).  One record per
  * cwslg_ft4_sync record of the SAME epoch, in the same order -- candidate order, then segment order: record q belongs to entry q of

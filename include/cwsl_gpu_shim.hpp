@@ -83,6 +83,15 @@ public:
     {
         check(c_, cwslg_enable_ft4_decode(c_, enable ? 1 : 0, maxIter, minNsync, minNqual));
     }
+    // FT8 OSD: ordered-statistics decoding (order 0..2) of the candidates the decode attempted without crc_ok, from the next boundary at which
+    // soft bits and decode are on too (needs a loaded code of rank 83) -- SsbChannel::fetchFt8Osd; osdDecode runs the same kernel on
+    // caller-supplied metrics
+    void enableFt8Osd(bool enable = true, int order = 2, int minNsync = 7) { check(c_, cwslg_enable_ft8_osd(c_, enable ? 1 : 0, order, minNsync)); }
+    void osdDecode(const float *llr, int n, std::vector<cwslg_osd_msg> &out, int order = 2)
+    {
+        out.resize(n);
+        check(c_, cwslg_osd_decode(c_, llr, n, order, out.data()));
+    }
     void synchronize() { check(c_, cwslg_synchronize(c_)); }
     // One block for each of several receivers in ONE call (cwslg_push_iq_many): for a host that serves thousands of streams, where a
     // per-receiver push per block (Receiver.hpp:242-249, ReceiverPort::push below) would mean hundreds of thousands of copies a second.
@@ -232,6 +241,18 @@ public:
         out.resize(max);
         int n = 0;
         const int rc = cwslg_fetch_ft4_decode(ctx_.raw(), id_, out.data(), max, &n, startEpoch);
+        if (rc == CWSLG_ERR_NO_FRAME) { out.clear(); return 0; }
+        check(ctx_.raw(), rc);
+        out.resize(n);
+        return n;
+    }
+    // FT8 channels with Context::enableFt8Osd: record q (91 bits, dmin, nharderr, nskip, crc_ok, how, flip) belongs to entry q of candidates() of
+    // the same epoch -- cwslg_fetch_ft8_osd; 0 records while none of the current epoch exist
+    int fetchFt8Osd(std::vector<cwslg_osd_msg> &out, int max = 600, std::uint64_t *startEpoch = nullptr)
+    {
+        out.resize(max);
+        int n = 0;
+        const int rc = cwslg_fetch_ft8_osd(ctx_.raw(), id_, out.data(), max, &n, startEpoch);
         if (rc == CWSLG_ERR_NO_FRAME) { out.clear(); return 0; }
         check(ctx_.raw(), rc);
         out.resize(n);
