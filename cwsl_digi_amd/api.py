@@ -128,6 +128,26 @@ OSD_MSG_DTYPE = np.dtype([("bits", np.uint8, 12), ("dmin", np.float32), ("nharde
                           ("flip", np.uint8, 2)])
 
 
+class Ft4Osd(C.Structure):
+    _fields_ = [("set", OsdMsg * 3)]
+
+
+# numpy view of cwslg_ft4_osd (72 bytes): three OSD_MSG_DTYPE records -- rec["set"]["crc_ok"][q, s] is set s of record q
+FT4_OSD_DTYPE = np.dtype([("set", OSD_MSG_DTYPE, 3)])
+
+
+def ft4_best_word(msg, osd):
+    """The word a consumer takes from FT4 decode records (FT4_MSG_DTYPE) and the OSD records of the same entries (FT4_OSD_DTYPE): the smallest s
+    with BP crc_ok (ft4_best_set); if there is none, the smallest s with OSD crc_ok, flagged by_osd (the bits are osd["set"][.., s]["bits"]
+    then); -1 if neither stage has a word.  One record -> (int, bool), arrays of records -> (int array, bool array)."""
+    bp = np.asarray(msg["set"]["crc_ok"]) != 0
+    ok = np.asarray(osd["set"]["crc_ok"]) != 0
+    has_bp = bp.any(axis=-1)
+    by_osd = ~has_bp & ok.any(axis=-1)
+    best = np.where(has_bp, bp.argmax(axis=-1), np.where(by_osd, ok.argmax(axis=-1), -1))
+    return (int(best), bool(by_osd)) if best.ndim == 0 else (best.astype(np.int64), by_osd)
+
+
 class Ft4Soft(C.Structure):
     _fields_ = [("llr", (C.c_float * 174) * 3), ("sigma", C.c_float * 3), ("nsync", C.c_int32), ("nqual", C.c_int32), ("pad_", C.c_int32)]
 
@@ -175,6 +195,7 @@ ABI_SYMBOLS = [
     "cwslg_enable_ft8_softbits", "cwslg_fetch_ft8_softbits", "cwslg_enable_ft4_softbits", "cwslg_fetch_ft4_softbits", "cwslg_sync_debug_fetch", "cwslg_get_stats", "cwslg_reset_stats",
     "cwslg_set_ldpc_code", "cwslg_enable_ft8_decode", "cwslg_fetch_ft8_decode", "cwslg_ldpc_decode",
     "cwslg_enable_ft8_osd", "cwslg_fetch_ft8_osd", "cwslg_osd_decode", "cwslg_enable_ft4_decode", "cwslg_fetch_ft4_decode",
+    "cwslg_enable_ft4_osd", "cwslg_fetch_ft4_osd",
     "cwslg_set_timing", "cwslg_demod_kernel_name", "cwslg_stream", "cwslg_channel_constants", "cwslg_phasor_checkpoint_stride", "cwslg_channel_phasor_checkpoints",
     "cwslg_slot_clock_next", "cwslg_pool_sizing", "cwslg_find_band", "cwslg_parse_decode_line",
     "cwslg_decoder_block_bytes", "cwslg_decoder_block_field", "cwslg_fill_decoder_block", "cwslg_decoder_route", "cwslg_decoder_command",
@@ -273,6 +294,8 @@ def load_library(build_if_missing=True):
     L.cwslg_fetch_ft4_softbits.argtypes = [vp, i32, C.POINTER(Ft4Soft), i32, C.POINTER(i32), C.POINTER(u64)]
     L.cwslg_enable_ft4_decode.argtypes = [vp, i32, i32, i32, i32]
     L.cwslg_fetch_ft4_decode.argtypes = [vp, i32, C.POINTER(Ft4Msg), i32, C.POINTER(i32), C.POINTER(u64)]
+    L.cwslg_enable_ft4_osd.argtypes = [vp, i32, i32, i32, i32]
+    L.cwslg_fetch_ft4_osd.argtypes = [vp, i32, C.POINTER(Ft4Osd), i32, C.POINTER(i32), C.POINTER(u64)]
     L.cwslg_sync_debug_fetch.argtypes = [vp, i32, i32, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(i32)]
     L.cwslg_get_stats.argtypes = [vp, C.POINTER(Stats)]
     L.cwslg_reset_stats.argtypes = [vp]
@@ -750,6 +773,26 @@ class Context:
         n = C.c_int()
         t0 = C.c_uint64()
         rc = self.L.cwslg_fetch_ft4_decode(self.h, ch, buf.ctypes.data_as(C.POINTER(Ft4Msg)), int(max_rec), C.byref(n), C.byref(t0))
+        if rc == ERR_NO_FRAME:
+            return None
+        self._chk(rc)
+        rec = buf[:n.value].copy()
+        return (rec, t0.value) if with_epoch else rec
+
+    def enable_ft4_osd(self, enable=True, order=2, min_nsync=8, min_nqual=20):
+        """Ordered-statistics decoding (order 0..2) of the metric sets of the FT4 records no set of which the decode brought to crc_ok
+        (cwslg_ft4_osd); needs a loaded code of rank 83; runs at boundaries where the coherent stage, enable_ft4_softbits and enable_ft4_decode are on
+        too."""
+        self._chk(self.L.cwslg_enable_ft4_osd(self.h, int(enable), int(order), int(min_nsync), int(min_nqual)))
+
+    def fetch_ft4_osd(self, ch, max_rec=1800, with_epoch=False):
+        """-> None unless OSD records of the channel's current epoch exist, else a numpy record array (FT4_OSD_DTYPE: rec["set"][q, s] is the
+        OSD_MSG_DTYPE record of metric set s) whose row q belongs to entry q of fetch_ft4_sync of the same epoch (with_epoch: (records, frame
+        start epoch)).  ft4_best_word picks the word a consumer takes from the decode and OSD records together."""
+        buf = np.zeros(max(int(max_rec), 1), FT4_OSD_DTYPE)
+        n = C.c_int()
+        t0 = C.c_uint64()
+        rc = self.L.cwslg_fetch_ft4_osd(self.h, ch, buf.ctypes.data_as(C.POINTER(Ft4Osd)), int(max_rec), C.byref(n), C.byref(t0))
         if rc == ERR_NO_FRAME:
             return None
         self._chk(rc)

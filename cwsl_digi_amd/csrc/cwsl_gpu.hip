@@ -208,6 +208,7 @@ struct Channel {
     uint64_t osd_t0 = 0;               // ... the FT8 OSD records were computed from (cwslg_enable_ft8_osd; 0: none)
     uint64_t msg_t0 = 0;               // ... the FT8 decode records were computed from (cwslg_enable_ft8_decode; 0: none)
     uint64_t msg4_t0 = 0;              // ... the FT4 decode records were computed from (cwslg_enable_ft4_decode; 0: none)
+    uint64_t osd4_t0 = 0;              // ... the FT4 OSD records were computed from (cwslg_enable_ft4_osd; 0: none)
     SyncChannelBuffers syncbuf;
 };
 

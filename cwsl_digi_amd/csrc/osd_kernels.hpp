@@ -17,6 +17,11 @@
 //   winner     min over (distance bits, word index): the index order IS the tie rule (c0, singles by i, pairs by (i, j)); six lane exchanges
 // Nothing is shared between waves, hence no workgroup barrier (ldpc_wave_sync fences); every exit is wave-uniform.
 // The same kernel serves cwslg_osd_decode: works == nullptr, n_flat sets of 174 metrics from llr_flat, no gates.
+// And the FT4 chain (cwslg_enable_ft4_osd), a third way of finding llr, out and the gate in front of the same code: works4 != nullptr, one wave per
+// (record slot, metric set) of ft4_softbits_kernel's slot array, grid (ceil(9 max_cand / 4), FT4 channels), addressed as ldpc_decode_kernel's
+// works4 branch addresses it: slot = q / 3, set s = q % 3, cand = slot / 3, r = slot % 3; the wave leaves if q >= 9 max_cand,
+// cand >= min(*ncand, max_cand) or r >= nrec[cand].  It writes set[s] of the slot's cwslg_ft4_osd (record q of the channel's array).  The gate is
+// per RECORD: set s is attempted iff its decode record was attempted, NO set of the slot has BP crc_ok, and nsync / nqual pass.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -26,6 +31,8 @@ namespace cwslg {
 
 constexpr int OSD_WAVES = 4;
 constexpr int OSD_NSINGLE = 1 + LDPC_K;                // c0 and the 91 single flips: word indices 0..91; pairs follow in (i, j) order
+struct Ft4OsdRec { OsdRec set[3]; };                   // = cwslg_ft4_osd
+static_assert(sizeof(Ft4OsdRec) == 72, "cwslg_ft4_osd is 72 bytes");
 
 // "the row has the bit": bm[] holds the position's bit in its word and 0 in the others (wave-uniform), so no register is indexed
 __device__ __forceinline__ bool osd_has(const uint32_t (&r)[OSD_GW], const uint32_t (&bm)[OSD_GW])
@@ -70,7 +77,9 @@ __device__ __forceinline__ uint64_t osd_key(float d, int k) { return ((uint64_t)
 __global__ __launch_bounds__(64 * OSD_WAVES) void osd_decode_kernel(const SyncWork *__restrict__ works, Ft8SoftRec *const *__restrict__ soft,
                                                                     Ft8MsgRec *const *__restrict__ msg, OsdRec *const *__restrict__ osd,
                                                                     const float *__restrict__ llr_flat, OsdRec *__restrict__ out_flat, int n_flat, int maxcand,
-                                                                    int order, int min_nsync, const OsdGen *__restrict__ gen)
+                                                                    int order, int min_nsync, const OsdGen *__restrict__ gen,
+                                                                    const Ft4Work *__restrict__ works4, Ft4SoftRec *const *__restrict__ soft4,
+                                                                    Ft4MsgRec *const *__restrict__ msg4, Ft4OsdRec *const *__restrict__ osd4, int min_nqual)
 {
     __shared__ __attribute__((aligned(16))) uint32_t s_gall[OSD_WAVES][LDPC_K * OSD_GW];
     __shared__ __attribute__((aligned(16))) float s_aall[OSD_WAVES][192];
@@ -89,6 +98,17 @@ __global__ __launch_bounds__(64 * OSD_WAVES) void osd_decode_kernel(const SyncWo
         llr = rec->llr;
         out = as_global_rw(osd[blockIdx.y]) + q;
         attempt = m->iters >= 0 && m->crc_ok == 0 && rec->nsync >= min_nsync;
+    } else if (works4) {
+        const Ft4Work *w = works4 + blockIdx.y;
+        if (q >= 9 * maxcand) return;                          // wave-uniform, all three
+        const int slot = q / 3, s = q - 3 * slot, cand = slot / 3, r = slot - 3 * cand;
+        if (cand >= min(*as_global(w->ncand), maxcand)) return;
+        if (r >= as_global(w->nrec)[cand]) return;
+        const CWSLG_GLOBAL Ft4SoftRec *rec = as_global(soft4[blockIdx.y]) + slot;
+        const CWSLG_GLOBAL Ft8MsgRec *m = as_global(&msg4[blockIdx.y]->set[0]) + 3 * slot;     // the slot's three decode records
+        llr = rec->llr[s];
+        out = as_global_rw(&osd4[blockIdx.y]->set[0]) + q;     // set s of slot q / 3
+        attempt = m[s].iters >= 0 && (m[0].crc_ok | m[1].crc_ok | m[2].crc_ok) == 0 && rec->nsync >= min_nsync && rec->nqual >= min_nqual;
     } else {
         if (q >= n_flat) return;
         llr = as_global(llr_flat) + (size_t)q * LDPC_N;

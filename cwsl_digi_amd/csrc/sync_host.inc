@@ -161,6 +161,18 @@ int ft4m_ensure_channel(cwslg_ctx *c, Channel &ch, bool want)
     return CWSLG_OK;
 }
 
+// The FT4 OSD records (osd_kernels.hpp's third addressing mode), [max_cand][3] cwslg_ft4_osd in the soft records' slot order, under the decode
+// records' rules: they exist only while the feature is on and follow max_cand (sync_ensure_channel frees everything when it changes).
+int ft4o_ensure_channel(cwslg_ctx *c, Channel &ch, bool want)
+{
+    SyncChannelBuffers &b = ch.syncbuf;
+    if ((b.d_ft4osd != nullptr) == want) return CWSLG_OK;
+    ch.osd4_t0 = 0;
+    if (!want) { (void)hipFree(b.d_ft4osd); b.d_ft4osd = nullptr; return CWSLG_OK; }
+    HIPCHK(c, hipMalloc((void **)&b.d_ft4osd, (size_t)b.max_cand * 3 * sizeof(Ft4OsdRec)));
+    return CWSLG_OK;
+}
+
 int sync_ensure_channel(cwslg_ctx *c, Channel &ch)
 {
     SyncChannelBuffers &b = ch.syncbuf;
@@ -178,6 +190,7 @@ int sync_ensure_channel(cwslg_ctx *c, Channel &ch)
     ch.osd_t0 = 0;
     ch.soft4_t0 = 0;
     ch.msg4_t0 = 0;
+    ch.osd4_t0 = 0;
     const size_t sp = ((size_t)(ch.sync_ft4 ? FT4_NHSYM : FT8_NHSYM) * want_bins * sizeof(float) + 255) & ~size_t(255);
     const size_t vec = ((size_t)(FT8_NH1 + 1) * 4 + 255) & ~size_t(255);
     const size_t cand = ((size_t)cfg.max_cand * sizeof(SyncChannelBuffers::Cand) + 255) & ~size_t(255);
@@ -229,19 +242,29 @@ void ldpc_launch_ft4(hipStream_t st, const void *tables, const Ft4Work *works4, 
                        max_iter, min_nsync, (const LdpcTables *)tables, works4, soft4, msg4, min_nqual);
 }
 
-// osd_decode_kernel's two addressing modes
+// osd_decode_kernel's three addressing modes
 //   FT8 chain: one wave per candidate of n_chan channels, behind the decode records it gates on
 void osd_launch_ft8(hipStream_t st, const void *gen, const SyncWork *works, Ft8SoftRec *const *soft, Ft8MsgRec *const *msg, OsdRec *const *osd, size_t n_chan,
                     int max_cand, int order, int min_nsync)
 {
     hipLaunchKernelGGL(osd_decode_kernel, dim3((unsigned)((max_cand + OSD_WAVES - 1) / OSD_WAVES), (unsigned)n_chan), dim3(64 * OSD_WAVES), 0, st, works, soft, msg, osd,
-                       (const float *)nullptr, (OsdRec *)nullptr, 0, max_cand, order, min_nsync, (const OsdGen *)gen);
+                       (const float *)nullptr, (OsdRec *)nullptr, 0, max_cand, order, min_nsync, (const OsdGen *)gen, (const Ft4Work *)nullptr,
+                       (Ft4SoftRec *const *)nullptr, (Ft4MsgRec *const *)nullptr, (Ft4OsdRec *const *)nullptr, 0);
 }
 //   flat: n sets of 174 metrics, no gate
 void osd_launch_flat(hipStream_t st, const void *gen, const float *llr, OsdRec *out, int n, int order)
 {
     hipLaunchKernelGGL(osd_decode_kernel, dim3((unsigned)((n + OSD_WAVES - 1) / OSD_WAVES), 1), dim3(64 * OSD_WAVES), 0, st, (const SyncWork *)nullptr,
-                       (Ft8SoftRec *const *)nullptr, (Ft8MsgRec *const *)nullptr, (OsdRec *const *)nullptr, llr, out, n, 0, order, 0, (const OsdGen *)gen);
+                       (Ft8SoftRec *const *)nullptr, (Ft8MsgRec *const *)nullptr, (OsdRec *const *)nullptr, llr, out, n, 0, order, 0, (const OsdGen *)gen,
+                       (const Ft4Work *)nullptr, (Ft4SoftRec *const *)nullptr, (Ft4MsgRec *const *)nullptr, (Ft4OsdRec *const *)nullptr, 0);
+}
+//   FT4 chain: one wave per (record slot, metric set) of n_chan channels, 9 max_cand waves per channel, behind the decode records it gates on
+void osd_launch_ft4(hipStream_t st, const void *gen, const Ft4Work *works4, Ft4SoftRec *const *soft4, Ft4MsgRec *const *msg4, Ft4OsdRec *const *osd4, size_t n_chan,
+                    int max_cand, int order, int min_nsync, int min_nqual)
+{
+    hipLaunchKernelGGL(osd_decode_kernel, dim3((unsigned)((9 * max_cand + OSD_WAVES - 1) / OSD_WAVES), (unsigned)n_chan), dim3(64 * OSD_WAVES), 0, st,
+                       (const SyncWork *)nullptr, (Ft8SoftRec *const *)nullptr, (Ft8MsgRec *const *)nullptr, (OsdRec *const *)nullptr, (const float *)nullptr,
+                       (OsdRec *)nullptr, 0, max_cand, order, min_nsync, (const OsdGen *)gen, works4, soft4, msg4, osd4, min_nqual);
 }
 
 // Run the sync stage on the frames finalised by this boundary: FT8 channels through the Costas search, FT4
@@ -255,6 +278,7 @@ int sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
     std::vector<Ft4Work> works4c;
     std::vector<Ft4SoftRec *> soft4;                          // cwslg_enable_ft4_softbits: one record array per FT4 channel, in works4c's order
     std::vector<Ft4MsgRec *> msg4;                            // cwslg_enable_ft4_decode (with the coherent stage and soft bits on): one record array per FT4 channel, in works4c's order
+    std::vector<Ft4OsdRec *> osd4;                            // cwslg_enable_ft4_osd (with the coherent stage, soft bits and decode on): one record array per FT4 channel, in works4c's order
     std::vector<Ft8SoftRec *> soft8;                          // cwslg_enable_ft8_softbits: one record array per FT8 channel, in works8's order
     std::vector<Ft8MsgRec *> msg8;                            // cwslg_enable_ft8_decode (with soft bits on): one record array per FT8 channel, in works8's order
     std::vector<OsdRec *> osd8;                               // cwslg_enable_ft8_osd (with soft bits and decode on): one record array per FT8 channel, in works8's order
@@ -296,12 +320,17 @@ int sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
             const bool soft = cfg.ft4_coherent && cfg.ft4_soft;
             if ((rc = ft4s_ensure_channel(c, ch, soft)) != CWSLG_OK) return rc;
             if ((rc = ft4m_ensure_channel(c, ch, soft && cfg.ft4_decode)) != CWSLG_OK) return rc;
+            if ((rc = ft4o_ensure_channel(c, ch, soft && cfg.ft4_decode && cfg.ft4_osd)) != CWSLG_OK) return rc;
             if (soft) {
                 soft4.push_back(ch.syncbuf.d_ft4soft);
                 ch.soft4_t0 = ch.frame_t0;                    // the soft-bit records now queued belong to this frame (feature or coherent stage off: the OLD epoch stays, nothing to fetch)
                 if (cfg.ft4_decode) {
                     msg4.push_back(ch.syncbuf.d_ft4msg);
                     ch.msg4_t0 = ch.frame_t0;                 // ... and the decode records, under the same rule
+                    if (cfg.ft4_osd) {
+                        osd4.push_back(ch.syncbuf.d_ft4osd);
+                        ch.osd4_t0 = ch.frame_t0;             // ... and the OSD records
+                    }
                 }
             }
         }
@@ -339,12 +368,15 @@ int sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
     WorkBuf *wb4 = nullptr;
     if (!works4c.empty()) {
         // (the FT4 soft-bit launch's record pointers ride behind the descriptors, as the FT8 ones do above)
-        const size_t wb4_bytes = works4c.size() * sizeof(Ft4Work) + soft4.size() * sizeof(Ft4SoftRec *) + msg4.size() * sizeof(Ft4MsgRec *);
+        const size_t wb4_bytes = works4c.size() * sizeof(Ft4Work) + soft4.size() * sizeof(Ft4SoftRec *) + msg4.size() * sizeof(Ft4MsgRec *) +
+                                 osd4.size() * sizeof(Ft4OsdRec *);
         wb4 = acquire_workbuf(c, wb4_bytes);
         if (!wb4) return fail(c, CWSLG_ERR_NOMEM, "work buffer allocation failed");
         std::memcpy(wb4->h, works4c.data(), works4c.size() * sizeof(Ft4Work));
         if (!soft4.empty()) std::memcpy((Ft4Work *)wb4->h + works4c.size(), soft4.data(), soft4.size() * sizeof(Ft4SoftRec *));
         if (!msg4.empty()) std::memcpy((Ft4SoftRec **)((Ft4Work *)wb4->h + works4c.size()) + soft4.size(), msg4.data(), msg4.size() * sizeof(Ft4MsgRec *));
+        if (!osd4.empty())
+            std::memcpy((Ft4SoftRec **)((Ft4Work *)wb4->h + works4c.size()) + soft4.size() + msg4.size(), osd4.data(), osd4.size() * sizeof(Ft4OsdRec *));
         HIPCHK(c, upload_workbuf(c, wb4, wb4_bytes));
     }
     hipEvent_t ea, eb;
@@ -495,6 +527,12 @@ int sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
                 ldpc_launch_ft4(c->stream, c->sync_shared.d_ldpc, f4, dsoft4, (Ft4MsgRec *const *)(dsoft4 + soft4.size()), n4, cfg.max_cand, cfg.ldpc4_max_iter,
                                 cfg.ldpc4_min_nsync, cfg.ldpc4_min_nqual);
                 c->stats.sync_launches++;
+                // OSD: one wave per (record slot, metric set) behind the decode records it gates on; counted as a launch of its own
+                if (!osd4.empty()) {
+                    osd_launch_ft4(c->stream, c->sync_shared.d_osdgen, f4, dsoft4, (Ft4MsgRec *const *)(dsoft4 + soft4.size()),
+                                   (Ft4OsdRec *const *)(dsoft4 + soft4.size() + msg4.size()), n4, cfg.max_cand, cfg.osd4_order, cfg.osd4_min_nsync, cfg.osd4_min_nqual);
+                    c->stats.sync_launches++;
+                }
             }
         }
     }
@@ -549,6 +587,8 @@ int cwslg_enable_sync(cwslg_ctx *c, int enable, float syncmin, int max_cand, int
         cfg.ft8_osd = c->sync_cfg.ft8_osd; cfg.osd_order = c->sync_cfg.osd_order; cfg.osd_min_nsync = c->sync_cfg.osd_min_nsync;
         cfg.ft4_decode = c->sync_cfg.ft4_decode; cfg.ldpc4_max_iter = c->sync_cfg.ldpc4_max_iter; cfg.ldpc4_min_nsync = c->sync_cfg.ldpc4_min_nsync;
         cfg.ldpc4_min_nqual = c->sync_cfg.ldpc4_min_nqual;
+        cfg.ft4_osd = c->sync_cfg.ft4_osd; cfg.osd4_order = c->sync_cfg.osd4_order; cfg.osd4_min_nsync = c->sync_cfg.osd4_min_nsync;
+        cfg.osd4_min_nqual = c->sync_cfg.osd4_min_nqual;
         if (cfg.ft8_soft) cfg.nbins = (cfg.ib + 15 + 31) / 32 * 32;   // soft bits on: tone 7 of bin ib (ib + 14) lies inside the row
         hipSetDevice(c->device);
         cfg.ft4_coherent = c->sync_cfg.ft4_coherent;
@@ -706,6 +746,7 @@ int cwslg_set_ldpc_code(cwslg_ctx *c, const uint8_t *nm)
         if (c->sync_shared.d_osdgen) HIPCHK(c, osd_upload_gen(c));      // (the streams are drained: no queued OSD launch still reads the old block)
     } else {
         c->sync_cfg.ft8_osd = false;
+        c->sync_cfg.ft4_osd = false;
     }
     return CWSLG_OK;
 }
@@ -1022,6 +1063,69 @@ int cwslg_fetch_ft4_decode(cwslg_ctx *c, int ch_id, cwslg_ft4_msg *dst, int max,
     for (int k = 0; k < cnt; ++k)                               // candidate order, then segment order: entry q of cwslg_fetch_ft4_sync
         for (int q = 0; q < nrec[k] && q < 3; ++q) {
             if (out < max) std::memcpy(&dst[out], &rec[(size_t)k * 3 + q], sizeof(Ft4MsgRec));
+            ++out;
+        }
+    *n = std::min(out, max);
+    return CWSLG_OK;
+}
+
+// FT4 OSD (osd_kernels.hpp's third addressing mode): one launch behind the FT4 decode launch, on the sets of the records no set of which BP
+// brought to crc_ok.
+int cwslg_enable_ft4_osd(cwslg_ctx *c, int enable, int order, int min_nsync, int min_nqual)
+{
+    if (!c) return CWSLG_ERR_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    SyncConfig &cfg = c->sync_cfg;
+    if (!enable) { cfg.ft4_osd = false; return CWSLG_OK; }
+    if (order < 0 || order > 2 || min_nsync < 0 || min_nsync > 17 || min_nqual < 0 || min_nqual > 33)
+        return fail(c, CWSLG_ERR_ARG, "FT4 OSD parameters out of range");
+    if (!c->sync_shared.osd_ready) return fail(c, CWSLG_ERR_ARG, "FT4 OSD needs a parity-check table of rank 83 (cwslg_set_ldpc_code)");
+    hipSetDevice(c->device);
+    HIPCHK(c, osd_upload_gen(c));
+    cfg.ft4_osd = true; cfg.osd4_order = order; cfg.osd4_min_nsync = min_nsync; cfg.osd4_min_nqual = min_nqual;
+    return CWSLG_OK;
+}
+
+// Handed out like the FT4 decode records (the same nrec walk over the same slot layout), and only together with them: OSD, decode and soft
+// records, sync records, list and frame of ONE epoch.
+int cwslg_fetch_ft4_osd(cwslg_ctx *c, int ch_id, cwslg_ft4_osd *dst, int max, int *n, uint64_t *start_epoch)
+{
+    if (!c || !n || (max > 0 && !dst)) return CWSLG_ERR_ARG;
+    *n = 0;
+    const int *cnt_src = nullptr, *nrec_src = nullptr;
+    const Ft4OsdRec *rec_src = nullptr;
+    int lim = 0;
+    ResultFetch rf;
+    {
+        std::lock_guard<std::mutex> g(c->mu);
+        if (ch_id < 0 || ch_id >= (int)c->chans.size() || !c->chans[ch_id].open) return fail(c, CWSLG_ERR_ARG, "bad channel id");
+        Channel &ch = c->chans[ch_id];
+        if (!ch.sync_ft4) return fail(c, CWSLG_ERR_MODE, "FT4 OSD records exist for FT4 channels only (mode %s)", ch.mode.c_str());
+        if (!ch.have_frame || !ch.syncbuf.d_block || !ch.syncbuf.d_ft4c || !ch.syncbuf.d_ft4soft || !ch.syncbuf.d_ft4msg || !ch.syncbuf.d_ft4osd ||
+            !ch.osd4_t0 || ch.osd4_t0 != ch.frame_t0 || ch.osd4_t0 != ch.cand_t0 || ch.osd4_t0 != ch.soft4_t0 || ch.osd4_t0 != ch.msg4_t0)
+            return CWSLG_ERR_NO_FRAME;
+        hipSetDevice(c->device);
+        if (start_epoch) *start_epoch = ch.osd4_t0;
+        cnt_src = ch.syncbuf.d_ncand; nrec_src = ch.syncbuf.d_nrec; rec_src = ch.syncbuf.d_ft4osd; lim = ch.syncbuf.max_cand;
+        int rc = begin_result_fetch(c, ch, rf);
+        if (rc) return rc;
+    }
+    static_assert(sizeof(cwslg_ft4_osd) == sizeof(Ft4OsdRec), "record layout");
+    int cnt = 0;
+    HIPCHK(c, hipStreamWaitEvent(rf.fs, rf.ev, 0));
+    HIPCHK(c, hipMemcpyAsync(&cnt, cnt_src, sizeof(int), hipMemcpyDeviceToHost, rf.fs));
+    HIPCHK(c, hipStreamSynchronize(rf.fs));
+    cnt = std::max(0, std::min(cnt, lim));
+    if (cnt <= 0) return CWSLG_OK;
+    std::vector<int> nrec((size_t)cnt);
+    std::vector<Ft4OsdRec> rec((size_t)cnt * 3);
+    HIPCHK(c, hipMemcpyAsync(nrec.data(), nrec_src, (size_t)cnt * sizeof(int), hipMemcpyDeviceToHost, rf.fs));
+    HIPCHK(c, hipMemcpyAsync(rec.data(), rec_src, (size_t)cnt * 3 * sizeof(Ft4OsdRec), hipMemcpyDeviceToHost, rf.fs));
+    HIPCHK(c, hipStreamSynchronize(rf.fs));
+    int out = 0;
+    for (int k = 0; k < cnt; ++k)                               // candidate order, then segment order: entry q of cwslg_fetch_ft4_sync
+        for (int q = 0; q < nrec[k] && q < 3; ++q) {
+            if (out < max) std::memcpy(&dst[out], &rec[(size_t)k * 3 + q], sizeof(Ft4OsdRec));
             ++out;
         }
     *n = std::min(out, max);

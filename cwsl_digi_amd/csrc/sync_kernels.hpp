@@ -51,6 +51,8 @@ struct SyncConfig {
     int ldpc4_max_iter = 30, ldpc4_min_nsync = 8, ldpc4_min_nqual = 20;
     bool ft8_osd = false;                 // cwslg_enable_ft8_osd: ordered-statistics decoding of the candidates the FT8 decode attempted without crc_ok (osd_kernels.hpp); runs only while ft8_soft and ft8_decode are on too
     int osd_order = 2, osd_min_nsync = 7;
+    bool ft4_osd = false;                 // cwslg_enable_ft4_osd: the same OSD on the sets of the FT4 records no set of which BP brought to crc_ok; runs only while ft4_coherent, ft4_soft and ft4_decode are on too
+    int osd4_order = 2, osd4_min_nsync = 8, osd4_min_nqual = 20;
 };
 
 struct SyncTables {                       // device pointers: W_NZ, W_128, 0.5 W_2NZ twiddles, optional window
@@ -69,7 +71,7 @@ struct SyncShared {
     void *d_ldpc = nullptr;               // LdpcTables (ldpc_host.hpp) derived from the caller's parity-check table; allocated by the first cwslg_set_ldpc_code
     bool ldpc_loaded = false;
     uint32_t osd_gen[91 * 6] = {};        // OsdGen (ldpc_host.hpp): a generator of the loaded code, derived with the tables while rank H = 83
-    void *d_osdgen = nullptr;             // its device copy: allocated by the first cwslg_enable_ft8_osd / cwslg_osd_decode, replaced by every later cwslg_set_ldpc_code
+    void *d_osdgen = nullptr;             // its device copy: allocated by the first cwslg_enable_ft8_osd / cwslg_enable_ft4_osd / cwslg_osd_decode, replaced by every later cwslg_set_ldpc_code
     bool osd_ready = false;               // the loaded code has rank 83: OSD may be enabled
     bool osd_dirty = false;               // osd_gen is newer than the device copy
 };
@@ -93,6 +95,7 @@ struct SyncChannelBuffers {
     int *d_nrec = nullptr;                // [max_cand]
     struct Ft4SoftRec *d_ft4soft = nullptr;   // [max_cand][3], the slot layout of d_rec; an allocation of its own, only while cwslg_enable_ft4_softbits is on
     struct Ft4MsgRec *d_ft4msg = nullptr;     // [max_cand][3], the same slot layout; an allocation of its own, only while soft bits AND cwslg_enable_ft4_decode are on
+    struct Ft4OsdRec *d_ft4osd = nullptr;     // [max_cand][3], the same slot layout; an allocation of its own, only while soft bits, decode AND cwslg_enable_ft4_osd are on
 };
 
 struct alignas(16) SyncWork {
@@ -113,6 +116,7 @@ inline void sync_free_channel(SyncChannelBuffers &b)
     if (b.d_ft4c) (void)hipFree(b.d_ft4c);
     if (b.d_ft4soft) (void)hipFree(b.d_ft4soft);
     if (b.d_ft4msg) (void)hipFree(b.d_ft4msg);
+    if (b.d_ft4osd) (void)hipFree(b.d_ft4osd);
     b = SyncChannelBuffers();
 }
 inline void sync_free_shared(SyncShared &s)

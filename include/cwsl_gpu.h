@@ -501,7 +501,8 @@ int cwslg_ldpc_decode(cwslg_ctx *ctx, const float *llr /* [n][174] */, int n, in
  * time.  cwslg_fetch_ft8_osd behaves like cwslg_fetch_ft8_decode: same ticket, record q belongs to list entry q, *n = min(list length, max),
  * CWSLG_ERR_MODE for a channel that is not FT8, CWSLG_ERR_NO_FRAME unless OSD, decode and soft-bit records, list and frame are of one epoch.
  * cwslg_osd_decode runs the same kernel on n >= 0 caller-supplied sets of 174 metrics (host memory) with no gates, synchronously; it returns
- * CWSLG_ERR_ARG without a loaded code of rank 83 or for an order outside 0..2.  The FT4 chain has no OSD stage yet. */
+ * CWSLG_ERR_ARG without a loaded code of rank 83 or for an order outside 0..2.  The FT4 chain has the same stage: FT4 OSD, behind the FT4 decode
+ * below. */
 typedef struct {
     uint8_t bits[12];     /* the winner's codeword positions 0..90, MSB first, as cwslg_ft8_msg.bits; the last 5 bits are 0           */
     float dmin;           /* the winner's distance d                                                                                 */
@@ -571,8 +572,8 @@ int cwslg_fetch_ft4_softbits(cwslg_ctx *ctx, int ch_id, cwslg_ft4_soft *dst, int
  *       all-zero codeword.  The three sets of a record are decoded side by side, each to its own exit.
  *   Which set "wins" is not stored.  Upstream tries the sets in order and stops at the first success: the smallest s with crc_ok
  *       (cwslgpu::ft4BestSet in cwsl_gpu_shim.hpp, ft4_best_set in the Python package; -1 if none).
- *   Out of scope: the rvec descrambling of the 77 message bits (the CRC is over the scrambled bits, so crc_ok does not need it), ordered-statistics
- *       decoding and a-priori passes, unpacking to text, de-duplication, extending cwslg_fetch_slot.
+ *   Out of scope: the rvec descrambling of the 77 message bits (the CRC is over the scrambled bits, so crc_ok does not need it), a-priori
+ *       passes, unpacking to text, de-duplication, extending cwslg_fetch_slot.  Ordered-statistics decoding is a stage of its own: FT4 OSD below.
  * cwslg_enable_ft4_decode(ctx, 1, max_iter 1..200 (upstream 30), min_nsync 0..17 (upstream 8), min_nqual 0..33 (upstream 20)) returns
  * CWSLG_ERR_ARG unless a code is loaded, the sync stage is on and FT4 soft bits are on; switching it off is always allowed.  min_nsync 17 or
  * min_nqual 33 mean "nothing is attempted", as min_nsync 22 does for FT8.  A boundary makes decode records only when the coherent stage, FT4
@@ -585,6 +586,32 @@ int cwslg_fetch_ft4_softbits(cwslg_ctx *ctx, int ch_id, cwslg_ft4_soft *dst, int
 typedef struct { cwslg_ft8_msg set[3]; } cwslg_ft4_msg;          /* 60 bytes */
 int cwslg_enable_ft4_decode(cwslg_ctx *ctx, int enable, int max_iter, int min_nsync, int min_nqual);
 int cwslg_fetch_ft4_decode(cwslg_ctx *ctx, int ch_id, cwslg_ft4_msg *dst, int max, int *n, uint64_t *start_epoch);
+/* FT4 OSD (PARITY UNPINNED, as FT8 OSD above): ordered-statistics decoding, order 0, 1 or 2, of the metric sets of the records the FT4 decode
+ * left without a word -- the last stage of the FT4 chain on the device, where the FT8 chain ends too: 72 bytes per record instead of a second
+ * fetch of its 2112 bytes of metrics, a choice of sets on the host and a blocking cwslg_osd_decode.  Off by default; while it is off nothing
+ * changes (launches, buffers, upload bytes, lists, records, frames).
+ *   Record: set[s], s = 0..2, is exactly what the contract of cwslg_osd_msg above yields for llr[s][0..173] of the record's cwslg_ft4_soft: the
+ *       same arithmetic, the same record, the same not-attempted record (also for a metric that is not finite).  Nothing of the OSD
+ *       arithmetic is restated or changed here.
+ *   Gate: set s of a record is attempted iff (1) its cwslg_ft8_msg (set[s] of the record's cwslg_ft4_msg) was attempted (iters >= 0), (2) NO
+ *       set of that record has BP crc_ok, and (3) the soft record has nsync >= min_nsync and nqual >= min_nqual.
+ *   The gate is per RECORD, not per set, on purpose: a record that BP decodes in set 1 alone does not have its sets 0 and 2 pushed through
+ *       4187 words each.  Every such search has roughly a 1 % chance of a false accept under the 14-bit CRC, and under upstream's set order
+ *       (first success wins) a false word in set 0 would be preferred to the true BP word in set 1.
+ *   Which word "wins" is not stored: the smallest s with BP crc_ok; if there is none, the smallest s with OSD crc_ok, marked as found by OSD
+ *       (cwslgpu::ft4BestWord in cwsl_gpu_shim.hpp, ft4_best_word in the Python package; -1 if none).  ft4BestSet / ft4_best_set are unchanged.
+ *   Out of scope: rvec descrambling, a-priori passes, unpacking to text, de-duplication, extending cwslg_fetch_slot.
+ * cwslg_enable_ft4_osd(ctx, 1, order 0..2, min_nsync 0..17, min_nqual 0..33) returns CWSLG_ERR_ARG unless a code of rank 83 is loaded and the
+ * arguments are in range (17 and 33 mean "nothing is attempted", as for cwslg_enable_ft4_decode); switching it off is always allowed.  It takes
+ * effect only at a boundary where the coherent stage, FT4 soft bits and the FT4 decode are all on: then one launch follows the decode launch on
+ * the same stream, the candidate and record counts read on the device.  That launch is counted in stats.sync_launches (a boundary with FT4
+ * channels alone then counts three).  cwslg_fetch_ft4_osd behaves like cwslg_fetch_ft4_decode: same ticket, the same walk over the records,
+ * record q belongs to entry q of cwslg_fetch_ft4_sync, *n = min(record count, max), CWSLG_ERR_MODE for a channel that is not FT4,
+ * CWSLG_ERR_NO_FRAME unless OSD, decode, soft and sync records, list and frame are of one epoch -- after a boundary that ran with OSD, the
+ * decode, the soft bits or the coherent stage off there is nothing to fetch, never an older slot's records under a newer epoch. */
+typedef struct { cwslg_osd_msg set[3]; } cwslg_ft4_osd;          /* 72 bytes */
+int cwslg_enable_ft4_osd(cwslg_ctx *ctx, int enable, int order, int min_nsync, int min_nqual);
+int cwslg_fetch_ft4_osd(cwslg_ctx *ctx, int ch_id, cwslg_ft4_osd *dst, int max, int *n, uint64_t *start_epoch);
 int cwslg_fetch_slot(cwslg_ctx *ctx, int ch_id, int16_t *frame, size_t cap, void *list, size_t list_bytes,
                      cwslg_ft4_sync *ft4, int max_ft4, cwslg_slot_result *out);
 int cwslg_set_ft4_syncmin(cwslg_ctx *ctx, float syncmin);

@@ -52,6 +52,21 @@ inline int ft4BestSet(const cwslg_ft4_msg &m)
     return -1;
 }
 
+// Which word a consumer takes from a record's cwslg_ft4_msg and cwslg_ft4_osd: the smallest s with BP crc_ok (ft4BestSet); if there is none, the
+// smallest s with OSD crc_ok, *byOsd = true (take osd.set[s].bits then, not msg.set[s].bits); -1 if neither stage has a word
+inline int ft4BestWord(const cwslg_ft4_msg &m, const cwslg_ft4_osd &o, bool *byOsd = nullptr)
+{
+    if (byOsd) *byOsd = false;
+    const int s = ft4BestSet(m);
+    if (s >= 0) return s;
+    for (int k = 0; k < 3; ++k)
+        if (o.set[k].crc_ok) {
+            if (byOsd) *byOsd = true;
+            return k;
+        }
+    return -1;
+}
+
 class Context {
 public:
     explicit Context(int device = -1) { check(nullptr, cwslg_create(&c_, device)); }
@@ -82,6 +97,12 @@ public:
     void enableFt4Decode(bool enable = true, int maxIter = 30, int minNsync = 8, int minNqual = 20)
     {
         check(c_, cwslg_enable_ft4_decode(c_, enable ? 1 : 0, maxIter, minNsync, minNqual));
+    }
+    // FT4 OSD: the same OSD on the metric sets of the FT4 records no set of which the decode brought to crc_ok, from the next boundary at which
+    // the coherent stage, soft bits and decode are on too (needs a loaded code of rank 83) -- SsbChannel::fetchFt4Osd, ft4BestWord
+    void enableFt4Osd(bool enable = true, int order = 2, int minNsync = 8, int minNqual = 20)
+    {
+        check(c_, cwslg_enable_ft4_osd(c_, enable ? 1 : 0, order, minNsync, minNqual));
     }
     // FT8 OSD: ordered-statistics decoding (order 0..2) of the candidates the decode attempted without crc_ok, from the next boundary at which
     // soft bits and decode are on too (needs a loaded code of rank 83) -- SsbChannel::fetchFt8Osd; osdDecode runs the same kernel on
@@ -241,6 +262,18 @@ public:
         out.resize(max);
         int n = 0;
         const int rc = cwslg_fetch_ft4_decode(ctx_.raw(), id_, out.data(), max, &n, startEpoch);
+        if (rc == CWSLG_ERR_NO_FRAME) { out.clear(); return 0; }
+        check(ctx_.raw(), rc);
+        out.resize(n);
+        return n;
+    }
+    // FT4 channels with Context::enableFt4Osd: record q (three cwslg_osd_msg, one per metric set) belongs to entry q of cwslg_fetch_ft4_sync of
+    // the same epoch -- cwslg_fetch_ft4_osd; 0 records while none of the current epoch exist
+    int fetchFt4Osd(std::vector<cwslg_ft4_osd> &out, int max = 1800, std::uint64_t *startEpoch = nullptr)
+    {
+        out.resize(max);
+        int n = 0;
+        const int rc = cwslg_fetch_ft4_osd(ctx_.raw(), id_, out.data(), max, &n, startEpoch);
         if (rc == CWSLG_ERR_NO_FRAME) { out.clear(); return 0; }
         check(ctx_.raw(), rc);
         out.resize(n);
