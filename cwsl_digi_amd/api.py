@@ -652,16 +652,19 @@ class Context:
     def enable_ft4_coherent(self, enable=True):
         self._chk(self.L.cwslg_enable_ft4_coherent(self.h, int(enable)))
 
-    def fetch_ft4_sync(self, ch, max_rec=1800):
-        """Refined FT4 candidates (ft4_downsample + sync4d search): list of dicts, candidate order then segment order."""
+    def fetch_ft4_sync(self, ch, max_rec=1800, with_epoch=False):
+        """Refined FT4 candidates (ft4_downsample + sync4d search): list of dicts, candidate order then segment order; None unless the coherent
+        stage ran on the list now on the device (with_epoch: (list, start epoch of the frame the records were computed from))."""
         buf = (Ft4Sync * max_rec)()
         n = C.c_int()
-        rc = self.L.cwslg_fetch_ft4_sync(self.h, ch, buf, max_rec, C.byref(n), None)
+        t0 = C.c_uint64()
+        rc = self.L.cwslg_fetch_ft4_sync(self.h, ch, buf, max_rec, C.byref(n), C.byref(t0))
         if rc == ERR_NO_FRAME:
             return None
         self._chk(rc)
-        return [dict(f0_hz=b.f0_hz, f1_hz=b.f1_hz, dt_s=b.dt_s, sync=b.sync, ibest=b.ibest, idf=b.idf, seg=b.seg, cand=b.cand)
-                for b in buf[:n.value]]
+        out = [dict(f0_hz=b.f0_hz, f1_hz=b.f1_hz, dt_s=b.dt_s, sync=b.sync, ibest=b.ibest, idf=b.idf, seg=b.seg, cand=b.cand)
+               for b in buf[:n.value]]
+        return (out, t0.value) if with_epoch else out
 
     def enable_ft8_softbits(self, enable=True):
         """Soft bits per FT8 sync candidate (cwslg_ft8_soft); needs enable_sync; applies from the next boundary on."""

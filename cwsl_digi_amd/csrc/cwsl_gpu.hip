@@ -203,6 +203,7 @@ struct Channel {
     size_t i16_end = ~size_t(0);       // d_i16 holds zeros at and beyond this index (the n_valid of the frame it holds); unknown until the first finalise
     // sync results
     uint64_t cand_t0 = 0;              // start epoch of the frame the candidate lists on the device were computed from (0: none yet)
+    uint64_t ft4c_t0 = 0;              // ... the FT4 sync records were computed from (cwslg_enable_ft4_coherent; 0: none)
     uint64_t soft_t0 = 0;              // ... the FT8 soft-bit records were computed from (cwslg_enable_ft8_softbits; 0: none)
     uint64_t soft4_t0 = 0;             // ... the FT4 soft-bit records were computed from (cwslg_enable_ft4_softbits; 0: none)
     uint64_t osd_t0 = 0;               // ... the FT8 OSD records were computed from (cwslg_enable_ft8_osd; 0: none)
@@ -2174,7 +2175,8 @@ int cwslg_fetch_slot(cwslg_ctx *c, int ch_id, int16_t *frame, size_t cap, void *
             if ((ch.sync_ft8 || ch.sync_ft4) && ch.syncbuf.d_block) {
                 kind = ch.sync_ft8 ? CWSLG_LIST_FT8 : CWSLG_LIST_FT4;
                 lsrc = ch.syncbuf.d_cand; lcnt = ch.syncbuf.d_ncand; item = sizeof(cwslg_candidate); max_cand = ch.syncbuf.max_cand;
-                if (ch.sync_ft4 && ch.syncbuf.d_ft4c) { nrec_src = ch.syncbuf.d_nrec; rec_src = (const char *)ch.syncbuf.d_rec; }
+                // (a boundary with the coherent stage off leaves d_rec / d_nrec as they were: no sync records of this epoch then)
+                if (ch.sync_ft4 && ch.syncbuf.d_ft4c && ch.ft4c_t0 == ch.frame_t0) { nrec_src = ch.syncbuf.d_nrec; rec_src = (const char *)ch.syncbuf.d_rec; }
             } else if ((ch.sync_wspr || ch.sync_fst4w) && ch.longbuf.d_block) {
                 kind = ch.sync_wspr ? CWSLG_LIST_WSPR : CWSLG_LIST_FST4W;
                 lsrc = ch.longbuf.w.cand; lcnt = ch.longbuf.w.ncand;

@@ -185,6 +185,7 @@ int sync_ensure_channel(cwslg_ctx *c, Channel &ch)
         (b.d_msg != nullptr) == want_msg && (b.d_osd != nullptr) == want_osd)
         return CWSLG_OK;
     sync_free_channel(b);
+    ch.ft4c_t0 = 0;
     ch.soft_t0 = 0;
     ch.msg_t0 = 0;
     ch.osd_t0 = 0;
@@ -315,6 +316,7 @@ int sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
             f.cand = ch.syncbuf.d_cand; f.ncand = ch.syncbuf.d_ncand;
             f.rec = (Ft4Rec *)ch.syncbuf.d_rec; f.nrec = ch.syncbuf.d_nrec; f.cd_dbg = ch.syncbuf.d_cd_dbg;
             works4c.push_back(f);
+            ch.ft4c_t0 = ch.frame_t0;                         // the sync records now queued belong to this frame (coherent stage off: the OLD epoch stays, nothing to fetch)
         }
         if (ch.sync_ft4) {
             const bool soft = cfg.ft4_coherent && cfg.ft4_soft;
@@ -922,9 +924,11 @@ int cwslg_fetch_ft4_sync(cwslg_ctx *c, int ch_id, cwslg_ft4_sync *dst, int max, 
         std::lock_guard<std::mutex> g(c->mu);
         if (ch_id < 0 || ch_id >= (int)c->chans.size() || !c->chans[ch_id].open) return fail(c, CWSLG_ERR_ARG, "bad channel id");
         Channel &ch = c->chans[ch_id];
-        if (!ch.have_frame || !ch.syncbuf.d_block || !ch.syncbuf.d_ft4c || !ch.cand_t0) return CWSLG_ERR_NO_FRAME;
+        // the records are walked under the list's count: both must be of ONE epoch (after a boundary that ran with the coherent stage off the
+        // list is new and d_rec / d_nrec are the older slot's -- nothing to fetch, never those records under the newer epoch)
+        if (!ch.have_frame || !ch.syncbuf.d_block || !ch.syncbuf.d_ft4c || !ch.ft4c_t0 || ch.ft4c_t0 != ch.cand_t0) return CWSLG_ERR_NO_FRAME;
         hipSetDevice(c->device);
-        if (start_epoch) *start_epoch = ch.cand_t0;
+        if (start_epoch) *start_epoch = ch.ft4c_t0;
         cnt_src = ch.syncbuf.d_ncand; nrec_src = ch.syncbuf.d_nrec; rec_src = (const char *)ch.syncbuf.d_rec; lim = ch.syncbuf.max_cand;
         int rc = begin_result_fetch(c, ch, rf);
         if (rc) return rc;

@@ -375,7 +375,10 @@ int cwslg_fetch_candidates(cwslg_ctx *ctx, int ch_id, cwslg_candidate *dst, int 
  * getcandidates4 candidate of an FT4 channel is band-limited to a 666.7 Hz complex baseband around its frequency and
  * correlated with the four 4x4 Costas blocks over ft4_decode's three start-time segments (coarse then fine grid in start
  * sample and frequency tweak).  One record per candidate and segment that passes (sync >= 1.2, not weaker than segment 1,
- * 10 < f1 < 4990), in candidate order then segment order.  Enabled by default whenever sync is enabled. */
+ * 10 < f1 < 4990), in candidate order then segment order.  Enabled by default whenever sync is enabled.  A boundary at
+ * which the stage is off makes a list and no records: until the next boundary with the stage on cwslg_fetch_ft4_sync
+ * returns CWSLG_ERR_NO_FRAME and cwslg_fetch_slot returns n_ft4_sync = 0 -- never an older slot's records under the
+ * newer epoch. */
 typedef struct {
     float   f0_hz;        /* the getcandidates4 candidate                                            */
     float   f1_hz;        /* f0 + best frequency tweak (Hz)                                          */
