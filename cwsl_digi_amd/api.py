@@ -612,14 +612,23 @@ class Context:
         """'sync' (default): strongest first, cut at max_cand in that order; 'freq': ascending frequency, cut in THAT order."""
         self._chk(self.L.cwslg_set_candidate_order(self.h, {"sync": 0, "freq": 1}[order]))
 
+    def _fetch_records(self, fn, ch, buf, max_items, none_without_frame=True):
+        """One list / record fetch of the C ABI into buf: -> (n, start epoch), or None for CWSLG_ERR_NO_FRAME (raised like every other error
+        with none_without_frame=False)."""
+        n = C.c_int()
+        t0 = C.c_uint64()
+        rc = fn(self.h, ch, buf, int(max_items), C.byref(n), C.byref(t0))
+        if rc == ERR_NO_FRAME and none_without_frame:
+            return None
+        self._chk(rc)
+        return n.value, t0.value
+
     def fetch_candidates(self, ch, max_cand=600, with_epoch=False):
         """[(freq_bin, time_step, sync, freq_hz, dt_s)]; with_epoch: (list, start epoch of the frame the list was computed from)."""
         buf = (Candidate * max_cand)()
-        n = C.c_int()
-        t0 = C.c_uint64()
-        self._chk(self.L.cwslg_fetch_candidates(self.h, ch, buf, max_cand, C.byref(n), C.byref(t0)))
-        out = [(buf[k].freq_bin, buf[k].time_step, buf[k].sync, buf[k].freq_hz, buf[k].dt_s) for k in range(n.value)]
-        return (out, t0.value) if with_epoch else out
+        n, t0 = self._fetch_records(self.L.cwslg_fetch_candidates, ch, buf, max_cand, none_without_frame=False)
+        out = [(buf[k].freq_bin, buf[k].time_step, buf[k].sync, buf[k].freq_hz, buf[k].dt_s) for k in range(n)]
+        return (out, t0) if with_epoch else out
 
     def fetch_slot(self, ch, max_list=1000, max_ft4=3000, want_frame=True):
         """cwslg_fetch_slot: frame + candidate list(s) of ONE epoch under one ticket.  -> None before the first frame, else a dict with
@@ -656,15 +665,13 @@ class Context:
         """Refined FT4 candidates (ft4_downsample + sync4d search): list of dicts, candidate order then segment order; None unless the coherent
         stage ran on the list now on the device (with_epoch: (list, start epoch of the frame the records were computed from))."""
         buf = (Ft4Sync * max_rec)()
-        n = C.c_int()
-        t0 = C.c_uint64()
-        rc = self.L.cwslg_fetch_ft4_sync(self.h, ch, buf, max_rec, C.byref(n), C.byref(t0))
-        if rc == ERR_NO_FRAME:
+        r = self._fetch_records(self.L.cwslg_fetch_ft4_sync, ch, buf, max_rec)
+        if r is None:
             return None
-        self._chk(rc)
+        n, t0 = r
         out = [dict(f0_hz=b.f0_hz, f1_hz=b.f1_hz, dt_s=b.dt_s, sync=b.sync, ibest=b.ibest, idf=b.idf, seg=b.seg, cand=b.cand)
-               for b in buf[:n.value]]
-        return (out, t0.value) if with_epoch else out
+               for b in buf[:n]]
+        return (out, t0) if with_epoch else out
 
     def enable_ft8_softbits(self, enable=True):
         """Soft bits per FT8 sync candidate (cwslg_ft8_soft); needs enable_sync; applies from the next boundary on."""
@@ -674,15 +681,13 @@ class Context:
         """-> None unless soft-bit records of the channel's current epoch exist, else (llr float32[n, 174], sigma float32[n], nsync int32[n]):
         row q belongs to entry q of fetch_candidates' list of the same epoch (with_epoch: the frame's start epoch as a fourth item)."""
         buf = np.zeros((max(int(max_cand), 1), 176), np.float32)          # one 704-byte record per row
-        n = C.c_int()
-        t0 = C.c_uint64()
-        rc = self.L.cwslg_fetch_ft8_softbits(self.h, ch, buf.ctypes.data_as(C.POINTER(Ft8Soft)), int(max_cand), C.byref(n), C.byref(t0))
-        if rc == ERR_NO_FRAME:
+        r = self._fetch_records(self.L.cwslg_fetch_ft8_softbits, ch, buf.ctypes.data_as(C.POINTER(Ft8Soft)), int(max_cand))
+        if r is None:
             return None
-        self._chk(rc)
-        rec = buf[:n.value]
+        n, t0 = r
+        rec = buf[:n]
         out = (np.ascontiguousarray(rec[:, :174]), rec[:, 174].copy(), rec[:, 175].copy().view(np.int32))
-        return out + (t0.value,) if with_epoch else out
+        return out + (t0,) if with_epoch else out
 
     def set_ldpc_code(self, nm):
         """Load the (174, 91) parity-check table: nm uint8[83, 7], 1-based codeword positions, a row of weight 6 ends in one 0 (the integrator's own
@@ -701,14 +706,12 @@ class Context:
         """-> None unless decode records of the channel's current epoch exist, else a numpy record array (FT8_MSG_DTYPE: bits uint8[12], iters, nbad,
         nharderr, crc_ok) whose row q belongs to entry q of fetch_candidates' list of the same epoch (with_epoch: (records, frame start epoch))."""
         buf = np.zeros(max(int(max_cand), 1), FT8_MSG_DTYPE)
-        n = C.c_int()
-        t0 = C.c_uint64()
-        rc = self.L.cwslg_fetch_ft8_decode(self.h, ch, buf.ctypes.data_as(C.POINTER(Ft8Msg)), int(max_cand), C.byref(n), C.byref(t0))
-        if rc == ERR_NO_FRAME:
+        r = self._fetch_records(self.L.cwslg_fetch_ft8_decode, ch, buf.ctypes.data_as(C.POINTER(Ft8Msg)), int(max_cand))
+        if r is None:
             return None
-        self._chk(rc)
-        rec = buf[:n.value].copy()
-        return (rec, t0.value) if with_epoch else rec
+        n, t0 = r
+        rec = buf[:n].copy()
+        return (rec, t0) if with_epoch else rec
 
     def ldpc_decode(self, llr, max_iter=30):
         """The decode kernel on caller-supplied metrics, llr float32[n, 174] (n >= 0), no nsync filter; synchronous.  -> record array [n]."""
@@ -727,14 +730,12 @@ class Context:
         nskip, crc_ok, how, flip uint8[2]) whose row q belongs to entry q of fetch_candidates' list of the same epoch (with_epoch: (records, frame
         start epoch))."""
         buf = np.zeros(max(int(max_cand), 1), OSD_MSG_DTYPE)
-        n = C.c_int()
-        t0 = C.c_uint64()
-        rc = self.L.cwslg_fetch_ft8_osd(self.h, ch, buf.ctypes.data_as(C.POINTER(OsdMsg)), int(max_cand), C.byref(n), C.byref(t0))
-        if rc == ERR_NO_FRAME:
+        r = self._fetch_records(self.L.cwslg_fetch_ft8_osd, ch, buf.ctypes.data_as(C.POINTER(OsdMsg)), int(max_cand))
+        if r is None:
             return None
-        self._chk(rc)
-        rec = buf[:n.value].copy()
-        return (rec, t0.value) if with_epoch else rec
+        n, t0 = r
+        rec = buf[:n].copy()
+        return (rec, t0) if with_epoch else rec
 
     def osd_decode(self, llr, order=2):
         """The OSD kernel on caller-supplied metrics, llr float32[n, 174] (n >= 0), no gates; synchronous.  -> record array [n]."""
@@ -752,16 +753,14 @@ class Context:
         nsync int32[n], nqual int32[n]): row q belongs to entry q of fetch_ft4_sync of the same epoch (with_epoch: the frame's start epoch
         as a fifth item)."""
         buf = np.zeros((max(int(max_rec), 1), 528), np.float32)           # one 2112-byte record per row
-        n = C.c_int()
-        t0 = C.c_uint64()
-        rc = self.L.cwslg_fetch_ft4_softbits(self.h, ch, buf.ctypes.data_as(C.POINTER(Ft4Soft)), int(max_rec), C.byref(n), C.byref(t0))
-        if rc == ERR_NO_FRAME:
+        r = self._fetch_records(self.L.cwslg_fetch_ft4_softbits, ch, buf.ctypes.data_as(C.POINTER(Ft4Soft)), int(max_rec))
+        if r is None:
             return None
-        self._chk(rc)
-        rec = buf[:n.value]
+        n, t0 = r
+        rec = buf[:n]
         out = (np.ascontiguousarray(rec[:, :522]).reshape(-1, 3, 174), np.ascontiguousarray(rec[:, 522:525]),
                rec[:, 525].copy().view(np.int32), rec[:, 526].copy().view(np.int32))
-        return out + (t0.value,) if with_epoch else out
+        return out + (t0,) if with_epoch else out
 
     def enable_ft4_decode(self, enable=True, max_iter=30, min_nsync=8, min_nqual=20):
         """LDPC decode + CRC-14 on the three metric sets of every FT4 soft-bit record (cwslg_ft4_msg); needs a loaded code, enable_sync and
@@ -773,14 +772,12 @@ class Context:
         FT8_MSG_DTYPE record of metric set s) whose row q belongs to entry q of fetch_ft4_sync of the same epoch (with_epoch: (records, frame
         start epoch)).  ft4_best_set picks the set upstream would take."""
         buf = np.zeros(max(int(max_rec), 1), FT4_MSG_DTYPE)
-        n = C.c_int()
-        t0 = C.c_uint64()
-        rc = self.L.cwslg_fetch_ft4_decode(self.h, ch, buf.ctypes.data_as(C.POINTER(Ft4Msg)), int(max_rec), C.byref(n), C.byref(t0))
-        if rc == ERR_NO_FRAME:
+        r = self._fetch_records(self.L.cwslg_fetch_ft4_decode, ch, buf.ctypes.data_as(C.POINTER(Ft4Msg)), int(max_rec))
+        if r is None:
             return None
-        self._chk(rc)
-        rec = buf[:n.value].copy()
-        return (rec, t0.value) if with_epoch else rec
+        n, t0 = r
+        rec = buf[:n].copy()
+        return (rec, t0) if with_epoch else rec
 
     def enable_ft4_osd(self, enable=True, order=2, min_nsync=8, min_nqual=20):
         """Ordered-statistics decoding (order 0..2) of the metric sets of the FT4 records no set of which the decode brought to crc_ok
@@ -793,14 +790,12 @@ class Context:
         OSD_MSG_DTYPE record of metric set s) whose row q belongs to entry q of fetch_ft4_sync of the same epoch (with_epoch: (records, frame
         start epoch)).  ft4_best_word picks the word a consumer takes from the decode and OSD records together."""
         buf = np.zeros(max(int(max_rec), 1), FT4_OSD_DTYPE)
-        n = C.c_int()
-        t0 = C.c_uint64()
-        rc = self.L.cwslg_fetch_ft4_osd(self.h, ch, buf.ctypes.data_as(C.POINTER(Ft4Osd)), int(max_rec), C.byref(n), C.byref(t0))
-        if rc == ERR_NO_FRAME:
+        r = self._fetch_records(self.L.cwslg_fetch_ft4_osd, ch, buf.ctypes.data_as(C.POINTER(Ft4Osd)), int(max_rec))
+        if r is None:
             return None
-        self._chk(rc)
-        rec = buf[:n.value].copy()
-        return (rec, t0.value) if with_epoch else rec
+        n, t0 = r
+        rec = buf[:n].copy()
+        return (rec, t0) if with_epoch else rec
 
     def enable_long_sync(self, on=True, nfa_hz=1400, nfb_hz=1600, minsync=1.2):
         """Candidate search of the 120 s modes (WSPR: wsprd's front end; FST4W-120: get_candidates_fst4 over nfa..nfb)."""
@@ -809,26 +804,22 @@ class Context:
     def fetch_wspr_candidates(self, ch, max_cand=200, with_epoch=False):
         """-> None until a frame was searched, else [(freq_hz, snr_db, drift, sync, shift)] (with_epoch: (list, frame start epoch))."""
         buf = (WsprCandidate * max_cand)()
-        n = C.c_int()
-        t0 = C.c_uint64()
-        rc = self.L.cwslg_fetch_wspr_candidates(self.h, ch, buf, max_cand, C.byref(n), C.byref(t0))
-        if rc == ERR_NO_FRAME:
+        r = self._fetch_records(self.L.cwslg_fetch_wspr_candidates, ch, buf, max_cand)
+        if r is None:
             return None
-        self._chk(rc)
-        out = [(b.freq_hz, b.snr_db, b.drift, b.sync, b.shift) for b in buf[:n.value]]
-        return (out, t0.value) if with_epoch else out
+        n, t0 = r
+        out = [(b.freq_hz, b.snr_db, b.drift, b.sync, b.shift) for b in buf[:n]]
+        return (out, t0) if with_epoch else out
 
     def fetch_fst4w_candidates(self, ch, max_cand=100, with_epoch=False):
         """-> None until a frame was searched, else [(freq_hz, snr, bin)] (with_epoch: (list, frame start epoch))."""
         buf = (Fst4wCandidate * max_cand)()
-        n = C.c_int()
-        t0 = C.c_uint64()
-        rc = self.L.cwslg_fetch_fst4w_candidates(self.h, ch, buf, max_cand, C.byref(n), C.byref(t0))
-        if rc == ERR_NO_FRAME:
+        r = self._fetch_records(self.L.cwslg_fetch_fst4w_candidates, ch, buf, max_cand)
+        if r is None:
             return None
-        self._chk(rc)
-        out = [(b.freq_hz, b.snr, b.bin) for b in buf[:n.value]]
-        return (out, t0.value) if with_epoch else out
+        n, t0 = r
+        out = [(b.freq_hz, b.snr, b.bin) for b in buf[:n]]
+        return (out, t0) if with_epoch else out
 
     def long_sync_debug(self, ch, what):
         """what: 'iq' complex64[46080], 'ps' float32[512, 359] (wsprd's ps[j][i]), 'smspec' float32[411] (WSPR);

@@ -44,6 +44,7 @@
 #include "host/slot_clock.hpp"
 #include "host/skimmer_config.hpp"
 #include "host/spot_parse.hpp"
+#include "record_kinds.hpp"
 #include "sync_kernels.hpp"
 #include "ft4sync_kernels.hpp"
 #include "ft8soft_kernels.hpp"
@@ -202,14 +203,8 @@ struct Channel {
     FinWork fused_fin{};
     size_t i16_end = ~size_t(0);       // d_i16 holds zeros at and beyond this index (the n_valid of the frame it holds); unknown until the first finalise
     // sync results
-    uint64_t cand_t0 = 0;              // start epoch of the frame the candidate lists on the device were computed from (0: none yet)
-    uint64_t ft4c_t0 = 0;              // ... the FT4 sync records were computed from (cwslg_enable_ft4_coherent; 0: none)
-    uint64_t soft_t0 = 0;              // ... the FT8 soft-bit records were computed from (cwslg_enable_ft8_softbits; 0: none)
-    uint64_t soft4_t0 = 0;             // ... the FT4 soft-bit records were computed from (cwslg_enable_ft4_softbits; 0: none)
-    uint64_t osd_t0 = 0;               // ... the FT8 OSD records were computed from (cwslg_enable_ft8_osd; 0: none)
-    uint64_t msg_t0 = 0;               // ... the FT8 decode records were computed from (cwslg_enable_ft8_decode; 0: none)
-    uint64_t msg4_t0 = 0;              // ... the FT4 decode records were computed from (cwslg_enable_ft4_decode; 0: none)
-    uint64_t osd4_t0 = 0;              // ... the FT4 OSD records were computed from (cwslg_enable_ft4_osd; 0: none)
+    uint64_t stamp[REC_KINDS] = {};    // per record kind (record_kinds.hpp): start epoch of the frame the records now on the device were computed from (0: none yet);
+                                       // written by sync_launch / long_sync_launch / sync_ensure_channel, read through records_epoch alone
     SyncChannelBuffers syncbuf;
 };
 
@@ -2171,20 +2166,19 @@ int cwslg_fetch_slot(cwslg_ctx *c, int ch_id, int16_t *frame, size_t cap, void *
         out->start_epoch = ch.frame_t0;
         out->n_valid = ch.frame_valid;
         src = ch.d_i16; fac_src = ch.d_factor; flen = ch.frame_len;
-        if (ch.cand_t0 == ch.frame_t0 && ch.cand_t0 != 0) {
-            if ((ch.sync_ft8 || ch.sync_ft4) && ch.syncbuf.d_block) {
-                kind = ch.sync_ft8 ? CWSLG_LIST_FT8 : CWSLG_LIST_FT4;
-                lsrc = ch.syncbuf.d_cand; lcnt = ch.syncbuf.d_ncand; item = sizeof(cwslg_candidate); max_cand = ch.syncbuf.max_cand;
-                // (a boundary with the coherent stage off leaves d_rec / d_nrec as they were: no sync records of this epoch then)
-                if (ch.sync_ft4 && ch.syncbuf.d_ft4c && ch.ft4c_t0 == ch.frame_t0) { nrec_src = ch.syncbuf.d_nrec; rec_src = (const char *)ch.syncbuf.d_rec; }
-            } else if ((ch.sync_wspr || ch.sync_fst4w) && ch.longbuf.d_block) {
-                kind = ch.sync_wspr ? CWSLG_LIST_WSPR : CWSLG_LIST_FST4W;
-                lsrc = ch.longbuf.w.cand; lcnt = ch.longbuf.w.ncand;
-                item = ch.sync_wspr ? sizeof(cwslg_wspr_candidate) : sizeof(cwslg_fst4w_candidate);
-                max_cand = ch.sync_wspr ? (int)WSPR_MAXCAND : (int)F4W_MAXCAND;
-            }
-            if (item) lim = (int)std::min<size_t>(list_bytes / item, (size_t)max_cand);
+        // with_frame: a list, and the FT4 sync records with it, only if of the frame's epoch
+        if ((ch.sync_ft8 || ch.sync_ft4) && channel_records_epoch(ch, REC_CAND, ch.syncbuf.d_block, true)) {
+            kind = ch.sync_ft8 ? CWSLG_LIST_FT8 : CWSLG_LIST_FT4;
+            lsrc = ch.syncbuf.d_cand; lcnt = ch.syncbuf.d_ncand; item = sizeof(cwslg_candidate); max_cand = ch.syncbuf.max_cand;
+            // (a boundary with the coherent stage off leaves d_rec / d_nrec as they were: no sync records of this epoch then)
+            if (ch.sync_ft4 && channel_records_epoch(ch, REC_FT4SYNC, ch.syncbuf.d_block, true)) { nrec_src = ch.syncbuf.d_nrec; rec_src = (const char *)ch.syncbuf.d_rec; }
+        } else if ((ch.sync_wspr || ch.sync_fst4w) && channel_records_epoch(ch, REC_CAND, ch.longbuf.d_block, true)) {
+            kind = ch.sync_wspr ? CWSLG_LIST_WSPR : CWSLG_LIST_FST4W;
+            lsrc = ch.longbuf.w.cand; lcnt = ch.longbuf.w.ncand;
+            item = ch.sync_wspr ? sizeof(cwslg_wspr_candidate) : sizeof(cwslg_fst4w_candidate);
+            max_cand = ch.sync_wspr ? (int)WSPR_MAXCAND : (int)F4W_MAXCAND;
         }
+        if (item) lim = (int)std::min<size_t>(list_bytes / item, (size_t)max_cand);
         int rc = begin_result_fetch(c, ch, rf);
         if (rc) return rc;
     }
@@ -2206,13 +2200,7 @@ int cwslg_fetch_slot(cwslg_ctx *c, int ch_id, int16_t *frame, size_t cap, void *
         HIPCHK(c, hipMemcpyAsync(nrec.data(), nrec_src, nrec.size() * sizeof(int), hipMemcpyDeviceToHost, rf.fs));
         HIPCHK(c, hipMemcpyAsync(rec.data(), rec_src, rec.size() * sizeof(Ft4Rec), hipMemcpyDeviceToHost, rf.fs));
         HIPCHK(c, hipStreamSynchronize(rf.fs));
-        int k_out = 0;
-        for (int k = 0; k < total; ++k)
-            for (int q = 0; q < nrec[k] && q < 3; ++q) {
-                if (k_out < max_ft4) std::memcpy(&ft4[k_out], &rec[(size_t)k * 3 + q], sizeof(Ft4Rec));
-                ++k_out;
-            }
-        out->n_ft4_sync = std::min(k_out, max_ft4);
+        out->n_ft4_sync = std::min(compact_records(ft4, sizeof(Ft4Rec), max_ft4, nrec.data(), (const char *)rec.data(), total), max_ft4);
     }
     return CWSLG_OK;
 }

@@ -176,7 +176,7 @@ int long_sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
         int rc = long_ensure_channel(c, ch);
         if (rc) return rc;
         (ch.sync_wspr ? ww : wf).push_back(ch.longbuf.w);
-        ch.cand_t0 = ch.frame_t0;       // the list now queued belongs to this frame
+        ch.stamp[REC_CAND] = ch.frame_t0;       // the list now queued belongs to this frame
     }
     if (ww.empty() && wf.empty()) return CWSLG_OK;
     int rc;
@@ -257,39 +257,6 @@ void long_free_shared(LongShared &s)
     s = LongShared();
 }
 
-int long_fetch_common(cwslg_ctx *c, int ch_id, bool wspr, void *dst, size_t item, int max, int *n, uint64_t *start_epoch)
-{
-    if (!c || !n || (max > 0 && !dst)) return CWSLG_ERR_ARG;
-    *n = 0;
-    const void *src = nullptr;
-    const int *cnt_src = nullptr;
-    int lim = 0;
-    ResultFetch rf;                                 // as cwslg_fetch_candidates: ticket of the S120 group, copies without the context mutex
-    {
-        std::lock_guard<std::mutex> g(c->mu);
-        if (ch_id < 0 || ch_id >= (int)c->chans.size() || !c->chans[ch_id].open) return fail(c, CWSLG_ERR_ARG, "bad channel id");
-        Channel &ch = c->chans[ch_id];
-        if ((wspr ? !ch.sync_wspr : !ch.sync_fst4w)) return fail(c, CWSLG_ERR_MODE, "channel mode %s has no such candidate list", ch.mode.c_str());
-        if (!ch.have_frame || !ch.longbuf.d_block || !ch.cand_t0) return CWSLG_ERR_NO_FRAME;
-        hipSetDevice(c->device);
-        if (start_epoch) *start_epoch = ch.cand_t0;
-        src = ch.longbuf.w.cand; cnt_src = ch.longbuf.w.ncand;
-        lim = std::min(std::max(max, 0), wspr ? (int)WSPR_MAXCAND : (int)F4W_MAXCAND);
-        int rc = begin_result_fetch(c, ch, rf);
-        if (rc) return rc;
-    }
-    int cnt = 0;
-    std::vector<char> tmp((size_t)lim * item);
-    HIPCHK(c, hipStreamWaitEvent(rf.fs, rf.ev, 0));
-    HIPCHK(c, hipMemcpyAsync(&cnt, cnt_src, sizeof(int), hipMemcpyDeviceToHost, rf.fs));
-    if (lim > 0) HIPCHK(c, hipMemcpyAsync(tmp.data(), src, (size_t)lim * item, hipMemcpyDeviceToHost, rf.fs));
-    HIPCHK(c, hipStreamSynchronize(rf.fs));
-    cnt = std::max(0, std::min(cnt, lim));
-    if (cnt > 0) std::memcpy(dst, tmp.data(), (size_t)cnt * item);
-    *n = cnt;
-    return CWSLG_OK;
-}
-
 } // namespace
 
 extern "C" {
@@ -310,13 +277,13 @@ int cwslg_enable_long_sync(cwslg_ctx *c, int enable, int fst4w_nfa_hz, int fst4w
 int cwslg_fetch_wspr_candidates(cwslg_ctx *c, int ch_id, cwslg_wspr_candidate *dst, int max, int *n, uint64_t *start_epoch)
 {
     static_assert(sizeof(cwslg_wspr_candidate) == sizeof(WsprCand), "candidate layout");
-    return long_fetch_common(c, ch_id, true, dst, sizeof(WsprCand), max, n, start_epoch);
+    return fetch_flat(c, ch_id, REC_CAND, CWSLG_LIST_WSPR, dst, sizeof(WsprCand), max, n, start_epoch);       // (sync_host.inc)
 }
 
 int cwslg_fetch_fst4w_candidates(cwslg_ctx *c, int ch_id, cwslg_fst4w_candidate *dst, int max, int *n, uint64_t *start_epoch)
 {
     static_assert(sizeof(cwslg_fst4w_candidate) == sizeof(Fst4wCand), "candidate layout");
-    return long_fetch_common(c, ch_id, false, dst, sizeof(Fst4wCand), max, n, start_epoch);
+    return fetch_flat(c, ch_id, REC_CAND, CWSLG_LIST_FST4W, dst, sizeof(Fst4wCand), max, n, start_epoch);
 }
 
 int cwslg_long_sync_debug_fetch(cwslg_ctx *c, int ch_id, int what, void *dst, size_t cap_bytes, size_t *n_items)

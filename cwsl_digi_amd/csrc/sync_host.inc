@@ -137,39 +137,16 @@ int ft4c_ensure_channel(cwslg_ctx *c, Channel &ch)
     return CWSLG_OK;
 }
 
-// The FT4 soft-bit records (ft4soft_kernels.hpp), [max_cand][3] in d_rec's slot layout: they exist only while the feature is on (a boundary
-// with it off frees them), go with the channel (sync_free_channel) and follow max_cand (sync_ensure_channel frees everything when it changes).
-int ft4s_ensure_channel(cwslg_ctx *c, Channel &ch, bool want)
+// A record array of the FT4 chain -- soft-bit (ft4soft_kernels.hpp), decode (ldpc_kernels.hpp) or OSD records (osd_kernels.hpp's third addressing
+// mode), [max_cand][3] in d_rec's slot layout, an allocation of its own: it exists only while its stage is queued (a boundary without it frees
+// it), goes with the channel (sync_free_channel) and follows max_cand (sync_ensure_channel frees everything when it changes).  A change either
+// way clears the kind's stamp: nothing to fetch until the stage has run on the new array.
+int ensure_record_array(cwslg_ctx *c, void **arr, uint64_t &stamp, size_t bytes, bool want)
 {
-    SyncChannelBuffers &b = ch.syncbuf;
-    if ((b.d_ft4soft != nullptr) == want) return CWSLG_OK;
-    ch.soft4_t0 = 0;
-    if (!want) { (void)hipFree(b.d_ft4soft); b.d_ft4soft = nullptr; return CWSLG_OK; }
-    HIPCHK(c, hipMalloc((void **)&b.d_ft4soft, (size_t)b.max_cand * 3 * sizeof(Ft4SoftRec)));
-    return CWSLG_OK;
-}
-
-// The FT4 decode records (ldpc_kernels.hpp), [max_cand][3] cwslg_ft4_msg in the soft records' slot order, under the soft records' rules: they
-// exist only while the feature is on and follow max_cand (sync_ensure_channel frees everything when it changes).
-int ft4m_ensure_channel(cwslg_ctx *c, Channel &ch, bool want)
-{
-    SyncChannelBuffers &b = ch.syncbuf;
-    if ((b.d_ft4msg != nullptr) == want) return CWSLG_OK;
-    ch.msg4_t0 = 0;
-    if (!want) { (void)hipFree(b.d_ft4msg); b.d_ft4msg = nullptr; return CWSLG_OK; }
-    HIPCHK(c, hipMalloc((void **)&b.d_ft4msg, (size_t)b.max_cand * 3 * sizeof(Ft4MsgRec)));
-    return CWSLG_OK;
-}
-
-// The FT4 OSD records (osd_kernels.hpp's third addressing mode), [max_cand][3] cwslg_ft4_osd in the soft records' slot order, under the decode
-// records' rules: they exist only while the feature is on and follow max_cand (sync_ensure_channel frees everything when it changes).
-int ft4o_ensure_channel(cwslg_ctx *c, Channel &ch, bool want)
-{
-    SyncChannelBuffers &b = ch.syncbuf;
-    if ((b.d_ft4osd != nullptr) == want) return CWSLG_OK;
-    ch.osd4_t0 = 0;
-    if (!want) { (void)hipFree(b.d_ft4osd); b.d_ft4osd = nullptr; return CWSLG_OK; }
-    HIPCHK(c, hipMalloc((void **)&b.d_ft4osd, (size_t)b.max_cand * 3 * sizeof(Ft4OsdRec)));
+    if ((*arr != nullptr) == want) return CWSLG_OK;
+    stamp = 0;
+    if (!want) { (void)hipFree(*arr); *arr = nullptr; return CWSLG_OK; }
+    HIPCHK(c, hipMalloc(arr, bytes));
     return CWSLG_OK;
 }
 
@@ -178,20 +155,14 @@ int sync_ensure_channel(cwslg_ctx *c, Channel &ch)
     SyncChannelBuffers &b = ch.syncbuf;
     const SyncConfig &cfg = c->sync_cfg;
     const int want_bins = ch.sync_ft4 ? FT4_ROW : cfg.nbins;
-    const bool want_soft = cfg.ft8_soft && ch.sync_ft8;      // the soft-bit records exist only while the feature is on (a later enable reallocates)
-    const bool want_msg = want_soft && cfg.ft8_decode;       // ... and so do the decode records
-    const bool want_osd = want_msg && cfg.ft8_osd;           // ... and the OSD records
+    const bool want_soft = cfg.kept.ft8_soft && ch.sync_ft8;      // the soft-bit records exist only while the feature is on (a later enable reallocates)
+    const bool want_msg = want_soft && cfg.kept.ft8_decode;       // ... and so do the decode records
+    const bool want_osd = want_msg && cfg.kept.ft8_osd;           // ... and the OSD records
     if (b.d_block && b.nbins == want_bins && b.max_cand == cfg.max_cand && b.ft4 == ch.sync_ft4 && (b.d_soft != nullptr) == want_soft &&
         (b.d_msg != nullptr) == want_msg && (b.d_osd != nullptr) == want_osd)
         return CWSLG_OK;
     sync_free_channel(b);
-    ch.ft4c_t0 = 0;
-    ch.soft_t0 = 0;
-    ch.msg_t0 = 0;
-    ch.osd_t0 = 0;
-    ch.soft4_t0 = 0;
-    ch.msg4_t0 = 0;
-    ch.osd4_t0 = 0;
+    for (int k = REC_CAND + 1; k < REC_KINDS; ++k) ch.stamp[k] = 0;      // (every stamp but the list's)
     const size_t sp = ((size_t)(ch.sync_ft4 ? FT4_NHSYM : FT8_NHSYM) * want_bins * sizeof(float) + 255) & ~size_t(255);
     const size_t vec = ((size_t)(FT8_NH1 + 1) * 4 + 255) & ~size_t(255);
     const size_t cand = ((size_t)cfg.max_cand * sizeof(SyncChannelBuffers::Cand) + 255) & ~size_t(255);
@@ -268,6 +239,29 @@ void osd_launch_ft4(hipStream_t st, const void *gen, const Ft4Work *works4, Ft4S
                        (OsdRec *)nullptr, 0, max_cand, order, min_nsync, (const OsdGen *)gen, works4, soft4, msg4, osd4, min_nqual);
 }
 
+// The record arrays of one chain (soft-bit, decode, OSD records) of the channels queued at a boundary, one pointer per channel and stage that is on,
+// in the order of the chain's descriptors.  place() writes the three pointer tables behind the descriptors of the chain's work buffer -- soft,
+// then decode, then OSD; a stage that is off adds no byte -- and keeps the device addresses the kernels take.
+template <class Soft, class Msg, class Osd> struct ChainArrays {
+    std::vector<Soft *> soft;
+    std::vector<Msg *> msg;
+    std::vector<Osd *> osd;
+    Soft *const *d_soft = nullptr;
+    Msg *const *d_msg = nullptr;
+    Osd *const *d_osd = nullptr;
+    size_t bytes() const { return (soft.size() + msg.size() + osd.size()) * sizeof(void *); }
+    void place(const WorkBuf *wb, size_t desc_bytes)
+    {
+        void **h = (void **)((char *)wb->h + desc_bytes), **d = (void **)((char *)wb->d + desc_bytes);
+        if (!soft.empty()) std::memcpy(h, soft.data(), soft.size() * sizeof(void *));
+        if (!msg.empty()) std::memcpy(h + soft.size(), msg.data(), msg.size() * sizeof(void *));
+        if (!osd.empty()) std::memcpy(h + soft.size() + msg.size(), osd.data(), osd.size() * sizeof(void *));
+        d_soft = (Soft *const *)d;
+        d_msg = (Msg *const *)(d + soft.size());
+        d_osd = (Osd *const *)(d + soft.size() + msg.size());
+    }
+};
+
 // Run the sync stage on the frames finalised by this boundary: FT8 channels through the Costas search, FT4
 // channels through getcandidates4's spectral-peak search.  Other modes have no sync stage.
 int sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
@@ -277,12 +271,11 @@ int sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
     const SyncConfig &cfg = c->sync_cfg;
     std::vector<SyncWork> works8, works4;
     std::vector<Ft4Work> works4c;
-    std::vector<Ft4SoftRec *> soft4;                          // cwslg_enable_ft4_softbits: one record array per FT4 channel, in works4c's order
-    std::vector<Ft4MsgRec *> msg4;                            // cwslg_enable_ft4_decode (with the coherent stage and soft bits on): one record array per FT4 channel, in works4c's order
-    std::vector<Ft4OsdRec *> osd4;                            // cwslg_enable_ft4_osd (with the coherent stage, soft bits and decode on): one record array per FT4 channel, in works4c's order
-    std::vector<Ft8SoftRec *> soft8;                          // cwslg_enable_ft8_softbits: one record array per FT8 channel, in works8's order
-    std::vector<Ft8MsgRec *> msg8;                            // cwslg_enable_ft8_decode (with soft bits on): one record array per FT8 channel, in works8's order
-    std::vector<OsdRec *> osd8;                               // cwslg_enable_ft8_osd (with soft bits and decode on): one record array per FT8 channel, in works8's order
+    ChainArrays<Ft8SoftRec, Ft8MsgRec, OsdRec> a8;            // the FT8 chain's record arrays, one per FT8 channel and stage that is on, in works8's order
+    ChainArrays<Ft4SoftRec, Ft4MsgRec, Ft4OsdRec> a4;         // the FT4 chain's (behind the coherent stage), in works4c's order
+    // the stages' switches by record kind: records_queued (record_kinds.hpp) says which of them run for a channel, each behind the one it reads from
+    const bool on[REC_KINDS] = {true, cfg.kept.ft4_coherent, cfg.kept.ft8_soft, cfg.kept.ft8_decode, cfg.kept.ft8_osd, cfg.kept.ft4_soft, cfg.kept.ft4_decode,
+                                cfg.kept.ft4_osd};
     for (int id : emitted) {
         Channel &ch = c->chans[id];
         if (!ch.sync_ft8 && !ch.sync_ft4) continue;
@@ -296,89 +289,66 @@ int sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
         w.cand = ch.syncbuf.d_cand; w.ncand = ch.syncbuf.d_ncand;
         if (ch.fin_fused) { w.fin = ch.fused_fin; ch.fin_fused = false; }       // the spectra kernel finalises this frame first (boundary_locked)
         (ch.sync_ft8 ? works8 : works4).push_back(w);
-        ch.cand_t0 = ch.frame_t0;     // the lists now queued belong to this frame
-        if (ch.sync_ft8 && cfg.ft8_soft) {
-            soft8.push_back(ch.syncbuf.d_soft);
-            ch.soft_t0 = ch.frame_t0;                         // ... and so do the soft-bit records (a boundary with the feature off leaves the OLD epoch: nothing to fetch)
-            if (cfg.ft8_decode) {
-                msg8.push_back(ch.syncbuf.d_msg);
-                ch.msg_t0 = ch.frame_t0;                      // ... and the decode records, under the same rule
-                if (cfg.ft8_osd) {
-                    osd8.push_back(ch.syncbuf.d_osd);
-                    ch.osd_t0 = ch.frame_t0;                  // ... and the OSD records
-                }
-            }
-        }
-        if (ch.sync_ft4 && cfg.ft4_coherent) {
+        const unsigned queued = records_queued(ch.sync_ft8, ch.sync_ft4, on);
+        auto runs = [&](int k) { return (queued & rec_bit(k)) != 0; };
+        SyncChannelBuffers &b = ch.syncbuf;
+        if (runs(REC_FT4SYNC)) {
             if ((rc = ft4c_ensure_tables(c)) != CWSLG_OK || (rc = ft4c_ensure_channel(c, ch)) != CWSLG_OK) return rc;
             Ft4Work f{};
-            f.frame = ch.d_i16; f.y = ch.syncbuf.d_y; f.cx = ch.syncbuf.d_cx;
-            f.cand = ch.syncbuf.d_cand; f.ncand = ch.syncbuf.d_ncand;
-            f.rec = (Ft4Rec *)ch.syncbuf.d_rec; f.nrec = ch.syncbuf.d_nrec; f.cd_dbg = ch.syncbuf.d_cd_dbg;
+            f.frame = ch.d_i16; f.y = b.d_y; f.cx = b.d_cx;
+            f.cand = b.d_cand; f.ncand = b.d_ncand;
+            f.rec = (Ft4Rec *)b.d_rec; f.nrec = b.d_nrec; f.cd_dbg = b.d_cd_dbg;
             works4c.push_back(f);
-            ch.ft4c_t0 = ch.frame_t0;                         // the sync records now queued belong to this frame (coherent stage off: the OLD epoch stays, nothing to fetch)
         }
         if (ch.sync_ft4) {
-            const bool soft = cfg.ft4_coherent && cfg.ft4_soft;
-            if ((rc = ft4s_ensure_channel(c, ch, soft)) != CWSLG_OK) return rc;
-            if ((rc = ft4m_ensure_channel(c, ch, soft && cfg.ft4_decode)) != CWSLG_OK) return rc;
-            if ((rc = ft4o_ensure_channel(c, ch, soft && cfg.ft4_decode && cfg.ft4_osd)) != CWSLG_OK) return rc;
-            if (soft) {
-                soft4.push_back(ch.syncbuf.d_ft4soft);
-                ch.soft4_t0 = ch.frame_t0;                    // the soft-bit records now queued belong to this frame (feature or coherent stage off: the OLD epoch stays, nothing to fetch)
-                if (cfg.ft4_decode) {
-                    msg4.push_back(ch.syncbuf.d_ft4msg);
-                    ch.msg4_t0 = ch.frame_t0;                 // ... and the decode records, under the same rule
-                    if (cfg.ft4_osd) {
-                        osd4.push_back(ch.syncbuf.d_ft4osd);
-                        ch.osd4_t0 = ch.frame_t0;             // ... and the OSD records
-                    }
-                }
-            }
+            const size_t slots = (size_t)b.max_cand * 3;
+            if ((rc = ensure_record_array(c, (void **)&b.d_ft4soft, ch.stamp[REC_SOFT4], slots * sizeof(Ft4SoftRec), runs(REC_SOFT4))) != CWSLG_OK) return rc;
+            if ((rc = ensure_record_array(c, (void **)&b.d_ft4msg, ch.stamp[REC_MSG4], slots * sizeof(Ft4MsgRec), runs(REC_MSG4))) != CWSLG_OK) return rc;
+            if ((rc = ensure_record_array(c, (void **)&b.d_ft4osd, ch.stamp[REC_OSD4], slots * sizeof(Ft4OsdRec), runs(REC_OSD4))) != CWSLG_OK) return rc;
         }
+        // what is queued now belongs to this frame; a stage that is off keeps its OLD stamp: nothing of it to fetch (record_kinds.hpp)
+        for (int k = 0; k < REC_KINDS; ++k)
+            if (runs(k)) ch.stamp[k] = ch.frame_t0;
+        if (runs(REC_SOFT8)) a8.soft.push_back(b.d_soft);
+        if (runs(REC_MSG8)) a8.msg.push_back(b.d_msg);
+        if (runs(REC_OSD8)) a8.osd.push_back(b.d_osd);
+        if (runs(REC_SOFT4)) a4.soft.push_back(b.d_ft4soft);
+        if (runs(REC_MSG4)) a4.msg.push_back(b.d_ft4msg);
+        if (runs(REC_OSD4)) a4.osd.push_back(b.d_ft4osd);
     }
     if (works8.empty() && works4.empty()) return CWSLG_OK;
     const size_t n8 = works8.size(), n4 = works4.size();
-    // the soft-bit launch's record pointers ride behind the descriptors in the same buffer (nothing is added while the feature is off)
-    const size_t wb_bytes = (n8 + n4) * sizeof(SyncWork) + soft8.size() * sizeof(Ft8SoftRec *) + msg8.size() * sizeof(Ft8MsgRec *) + osd8.size() * sizeof(OsdRec *);
+    // the FT8 chain's record pointers ride behind the descriptors in the same buffer (nothing is added while the feature is off)
+    const size_t wb_bytes = (n8 + n4) * sizeof(SyncWork) + a8.bytes();
     WorkBuf *wb = acquire_workbuf(c, wb_bytes);
     if (!wb) return fail(c, CWSLG_ERR_NOMEM, "work buffer allocation failed");
     if (n8) std::memcpy(wb->h, works8.data(), n8 * sizeof(SyncWork));
     if (n4) std::memcpy((SyncWork *)wb->h + n8, works4.data(), n4 * sizeof(SyncWork));
-    if (!soft8.empty()) std::memcpy((SyncWork *)wb->h + n8 + n4, soft8.data(), soft8.size() * sizeof(Ft8SoftRec *));
-    if (!msg8.empty()) std::memcpy((Ft8SoftRec **)((SyncWork *)wb->h + n8 + n4) + soft8.size(), msg8.data(), msg8.size() * sizeof(Ft8MsgRec *));
-    if (!osd8.empty()) std::memcpy((Ft8SoftRec **)((SyncWork *)wb->h + n8 + n4) + soft8.size() + msg8.size(), osd8.data(), osd8.size() * sizeof(OsdRec *));
+    a8.place(wb, (n8 + n4) * sizeof(SyncWork));
     HIPCHK(c, upload_workbuf(c, wb, wb_bytes));
     // one wave per candidate behind whichever search form wrote d_cand / d_ncand (the count is read on the device); its time is part of the
     // stage's span (stats.sync_ms), not of the search's own
     auto launch_soft = [&](hipStream_t st) {
-        if (soft8.empty()) return;
+        if (a8.soft.empty()) return;
         hipLaunchKernelGGL(ft8_softbits_kernel, dim3((unsigned)((cfg.max_cand + FT8S_WAVES - 1) / FT8S_WAVES), (unsigned)n8), dim3(64 * FT8S_WAVES), 0, st,
-                           (const SyncWork *)wb->d, (Ft8SoftRec *const *)((const SyncWork *)wb->d + n8 + n4), cfg.nbins, cfg.max_cand);
+                           (const SyncWork *)wb->d, a8.d_soft, cfg.nbins, cfg.max_cand);
         // the decode: one wave per candidate behind the metrics it reads (same grid, same device-side count); counted as a launch of its own
-        if (msg8.empty()) return;
-        Ft8SoftRec *const *dsoft = (Ft8SoftRec *const *)((const SyncWork *)wb->d + n8 + n4);
-        ldpc_launch_ft8(st, c->sync_shared.d_ldpc, (const SyncWork *)wb->d, dsoft, (Ft8MsgRec *const *)(dsoft + n8), n8, cfg.max_cand, cfg.ldpc_max_iter,
-                        cfg.ldpc_min_nsync);
+        if (a8.msg.empty()) return;
+        ldpc_launch_ft8(st, c->sync_shared.d_ldpc, (const SyncWork *)wb->d, a8.d_soft, a8.d_msg, n8, cfg.max_cand, cfg.kept.ldpc_max_iter, cfg.kept.ldpc_min_nsync);
         c->stats.sync_launches++;
         // OSD: one wave per candidate behind the decode records it gates on; counted as a launch of its own
-        if (osd8.empty()) return;
-        osd_launch_ft8(st, c->sync_shared.d_osdgen, (const SyncWork *)wb->d, dsoft, (Ft8MsgRec *const *)(dsoft + n8), (OsdRec *const *)(dsoft + 2 * n8), n8, cfg.max_cand,
-                       cfg.osd_order, cfg.osd_min_nsync);
+        if (a8.osd.empty()) return;
+        osd_launch_ft8(st, c->sync_shared.d_osdgen, (const SyncWork *)wb->d, a8.d_soft, a8.d_msg, a8.d_osd, n8, cfg.max_cand, cfg.kept.osd_order, cfg.kept.osd_min_nsync);
         c->stats.sync_launches++;
     };
     WorkBuf *wb4 = nullptr;
     if (!works4c.empty()) {
-        // (the FT4 soft-bit launch's record pointers ride behind the descriptors, as the FT8 ones do above)
-        const size_t wb4_bytes = works4c.size() * sizeof(Ft4Work) + soft4.size() * sizeof(Ft4SoftRec *) + msg4.size() * sizeof(Ft4MsgRec *) +
-                                 osd4.size() * sizeof(Ft4OsdRec *);
+        // (the FT4 chain's record pointers ride behind the descriptors, as the FT8 ones do above)
+        const size_t wb4_bytes = works4c.size() * sizeof(Ft4Work) + a4.bytes();
         wb4 = acquire_workbuf(c, wb4_bytes);
         if (!wb4) return fail(c, CWSLG_ERR_NOMEM, "work buffer allocation failed");
         std::memcpy(wb4->h, works4c.data(), works4c.size() * sizeof(Ft4Work));
-        if (!soft4.empty()) std::memcpy((Ft4Work *)wb4->h + works4c.size(), soft4.data(), soft4.size() * sizeof(Ft4SoftRec *));
-        if (!msg4.empty()) std::memcpy((Ft4SoftRec **)((Ft4Work *)wb4->h + works4c.size()) + soft4.size(), msg4.data(), msg4.size() * sizeof(Ft4MsgRec *));
-        if (!osd4.empty())
-            std::memcpy((Ft4SoftRec **)((Ft4Work *)wb4->h + works4c.size()) + soft4.size() + msg4.size(), osd4.data(), osd4.size() * sizeof(Ft4OsdRec *));
+        a4.place(wb4, works4c.size() * sizeof(Ft4Work));
         HIPCHK(c, upload_workbuf(c, wb4, wb4_bytes));
     }
     hipEvent_t ea, eb;
@@ -448,10 +418,10 @@ int sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
         hipEvent_t qa = nullptr, qb = nullptr;
         if (s8 == c->stream) span_begin(c, 4, &qa, &qb);
         if (per_channel) {
-            hipLaunchKernelGGL(ft8_sync_chan_kernel, dim3((unsigned)n8), dim3(SYNCC_NT), 0, s8, d8, cfg.ia, cfg.ib, cfg.nbins, cfg.syncmin, cfg.max_cand, cfg.order);
+            hipLaunchKernelGGL(ft8_sync_chan_kernel, dim3((unsigned)n8), dim3(SYNCC_NT), 0, s8, d8, cfg.ia, cfg.ib, cfg.nbins, cfg.syncmin, cfg.max_cand, cfg.kept.order);
         } else {
             hipLaunchKernelGGL(ft8_sync2d_v3_kernel, dim3(nbands, (unsigned)n8), dim3(SYNC2D_NT), 0, s8, d8, cfg.ia, cfg.ib, cfg.nbins);
-            hipLaunchKernelGGL(ft8_candidates_kernel<1024>, dim3((unsigned)n8), dim3(1024), 0, s8, d8, cfg.ia, cfg.ib, cfg.syncmin, cfg.max_cand, cfg.order);
+            hipLaunchKernelGGL(ft8_candidates_kernel<1024>, dim3((unsigned)n8), dim3(1024), 0, s8, d8, cfg.ia, cfg.ib, cfg.syncmin, cfg.max_cand, cfg.kept.order);
         }
         span_end(c, qb);
         launch_soft(s8);
@@ -476,10 +446,10 @@ int sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
         }
         if (c->sync_variant & 4)           // CWSLG_SYNC_VARIANT bit 2: 256 threads per channel, as in round 1
             hipLaunchKernelGGL(ft8_candidates_kernel<256>, dim3((unsigned)n8), dim3(256), 0, cs, d8, cfg.ia, cfg.ib,
-                               cfg.syncmin, cfg.max_cand, cfg.order);
+                               cfg.syncmin, cfg.max_cand, cfg.kept.order);
         else
             hipLaunchKernelGGL(ft8_candidates_kernel<1024>, dim3((unsigned)n8), dim3(1024), 0, cs, d8, cfg.ia, cfg.ib,
-                               cfg.syncmin, cfg.max_cand, cfg.order);
+                               cfg.syncmin, cfg.max_cand, cfg.kept.order);
         launch_soft(cs);
         if (cand_async) {
             if (sb) hipEventRecord(sb, c->side);
@@ -506,8 +476,8 @@ int sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
         hipLaunchKernelGGL((symbol_spectra_v2_kernel<9, FT4_NFFT1, FT4_NSTEP, true>), dim3((FT4_NHSYM + jper4 - 1) / jper4, (unsigned)n4), dim3(256), 0,
                            c->stream, d4, c->sync_shared.t4, FT4_ROW, FT4_NHSYM, jper4);
         hipLaunchKernelGGL(ft4_candidates_kernel, dim3((unsigned)n4), dim3(256), 0, c->stream, d4, nfa, nfb,
-                           c->sync_cfg.syncmin_ft4, cfg.max_cand, cfg.order);
-        if (c->sync_cfg.ft4_coherent) {
+                           c->sync_cfg.syncmin_ft4, cfg.max_cand, cfg.kept.order);
+        if (c->sync_cfg.kept.ft4_coherent) {
             // the coherent stage of ft4_decode on every candidate: frame spectrum, then one workgroup per candidate
             const Ft4Work *f4 = (const Ft4Work *)wb4->d;
 #if CWSLG_LAB
@@ -519,20 +489,19 @@ int sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
             hipLaunchKernelGGL(ft4_fft64_unpack_kernel, dim3(284, (unsigned)n4), dim3(64), 0, c->stream, f4, c->ft4_tables);
             hipLaunchKernelGGL(ft4_refine_kernel, dim3((unsigned)cfg.max_cand, (unsigned)n4), dim3(256), 0, c->stream, f4, c->ft4_tables, cfg.max_cand);
             // soft bits: one workgroup per record slot behind the refinement; nrec and the candidate count are read on the device
-            if (!soft4.empty())
-                hipLaunchKernelGGL(ft4_softbits_kernel, dim3(3u * (unsigned)cfg.max_cand, (unsigned)n4), dim3(256), 0, c->stream, f4,
-                                   (Ft4SoftRec *const *)(f4 + works4c.size()), c->ft4_tables, c->sync_shared.ft4_w32, cfg.max_cand);
+            if (!a4.soft.empty())
+                hipLaunchKernelGGL(ft4_softbits_kernel, dim3(3u * (unsigned)cfg.max_cand, (unsigned)n4), dim3(256), 0, c->stream, f4, a4.d_soft, c->ft4_tables,
+                                   c->sync_shared.ft4_w32, cfg.max_cand);
             // the decode: one wave per (record slot, metric set) behind the metrics it reads, the counts read on the device as the launch above
             // reads them; counted as a launch of its own, as the FT8 decode's is
-            if (!msg4.empty()) {
-                Ft4SoftRec *const *dsoft4 = (Ft4SoftRec *const *)(f4 + works4c.size());
-                ldpc_launch_ft4(c->stream, c->sync_shared.d_ldpc, f4, dsoft4, (Ft4MsgRec *const *)(dsoft4 + soft4.size()), n4, cfg.max_cand, cfg.ldpc4_max_iter,
-                                cfg.ldpc4_min_nsync, cfg.ldpc4_min_nqual);
+            if (!a4.msg.empty()) {
+                ldpc_launch_ft4(c->stream, c->sync_shared.d_ldpc, f4, a4.d_soft, a4.d_msg, n4, cfg.max_cand, cfg.kept.ldpc4_max_iter, cfg.kept.ldpc4_min_nsync,
+                                cfg.kept.ldpc4_min_nqual);
                 c->stats.sync_launches++;
                 // OSD: one wave per (record slot, metric set) behind the decode records it gates on; counted as a launch of its own
-                if (!osd4.empty()) {
-                    osd_launch_ft4(c->stream, c->sync_shared.d_osdgen, f4, dsoft4, (Ft4MsgRec *const *)(dsoft4 + soft4.size()),
-                                   (Ft4OsdRec *const *)(dsoft4 + soft4.size() + msg4.size()), n4, cfg.max_cand, cfg.osd4_order, cfg.osd4_min_nsync, cfg.osd4_min_nqual);
+                if (!a4.osd.empty()) {
+                    osd_launch_ft4(c->stream, c->sync_shared.d_osdgen, f4, a4.d_soft, a4.d_msg, a4.d_osd, n4, cfg.max_cand, cfg.kept.osd4_order, cfg.kept.osd4_min_nsync,
+                                   cfg.kept.osd4_min_nqual);
                     c->stats.sync_launches++;
                 }
             }
@@ -564,6 +533,130 @@ int sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
     return CWSLG_OK;
 }
 
+// ---- the list and record fetches ------------------------------------------------------------------------------------------------------------
+// Lists and records are handed out the way cwslg_fetch_frame hands a frame out (ABI 5): under the context mutex only the pointers are read and
+// a ticket of the channel's group is taken (fetch_begin); the copies run on a fetch stream behind the group's generation event with the mutex
+// released (a fetch during a 30 ms demod launch does not block every pusher), and the group's next boundary -- the next writer of the buffers --
+// waits for the ticket.  *start_epoch is the start epoch of the frame the records were computed from.  WHAT may be handed out, and under which
+// epoch, is the kind table's business (record_kinds.hpp); HOW it is copied out is one of two bodies: fetch_flat (a count, then that many
+// items) and fetch_walk (the FT4 chain's slot layout, compacted by the nrec walk).
+
+// The array of kind k (REC_CAND: the list, inside d_block; REC_FT4SYNC: d_rec, inside d_ft4c)
+const void *record_array(const SyncChannelBuffers &b, int k)
+{
+    switch (k) {
+    case REC_CAND: return b.d_cand;
+    case REC_FT4SYNC: return b.d_rec;
+    case REC_SOFT8: return b.d_soft;
+    case REC_MSG8: return b.d_msg;
+    case REC_OSD8: return b.d_osd;
+    case REC_SOFT4: return b.d_ft4soft;
+    case REC_MSG4: return b.d_ft4msg;
+    case REC_OSD4: return b.d_ft4osd;
+    }
+    return nullptr;
+}
+
+// records_epoch on a channel.  list_block: the block that holds the list in question -- syncbuf.d_block, or longbuf.d_block for a 120 s list.
+uint64_t channel_records_epoch(const Channel &ch, int k, const void *list_block, bool with_frame = false)
+{
+    unsigned present = list_block ? rec_bit(REC_CAND) : 0;
+    for (int j = REC_CAND + 1; j < REC_KINDS; ++j)
+        if (record_array(ch.syncbuf, j)) present |= rec_bit(j);
+    return records_epoch(k, ch.have_frame, ch.frame_t0, ch.stamp, present, with_frame);
+}
+
+struct RecSource {
+    const void *rec = nullptr;          // the records (flat: [cap]; walk: [cap][3])
+    const int *cnt = nullptr;           // the list's count
+    const int *nrec = nullptr;          // walk: records per candidate, [cap]
+    int cap = 0;                        // the list limit the arrays were sized for
+};
+
+// The part of a fetch under the context mutex: channel, mode gate, the rule, *start_epoch, the device pointers and the ticket.  long_list: 0, or
+// CWSLG_LIST_WSPR / CWSLG_LIST_FST4W for the list of a 120 s channel (kind REC_CAND, buffers of the channel's longbuf).
+int fetch_begin(cwslg_ctx *c, int ch_id, int k, int long_list, uint64_t *start_epoch, RecSource &s, ResultFetch &rf)
+{
+    std::lock_guard<std::mutex> g(c->mu);
+    if (ch_id < 0 || ch_id >= (int)c->chans.size() || !c->chans[ch_id].open) return fail(c, CWSLG_ERR_ARG, "bad channel id");
+    Channel &ch = c->chans[ch_id];
+    const RecKindRow &row = kRecKinds[k];
+    if (long_list) {
+        if (long_list == CWSLG_LIST_WSPR ? !ch.sync_wspr : !ch.sync_fst4w)
+            return fail(c, CWSLG_ERR_MODE, "channel mode %s has no such candidate list", ch.mode.c_str());
+    } else if (row.gate && !(row.chain == CHAIN_FT8 ? ch.sync_ft8 : ch.sync_ft4)) {
+        return fail(c, CWSLG_ERR_MODE, row.gate, ch.mode.c_str());
+    }
+    const uint64_t t0 = channel_records_epoch(ch, k, long_list ? ch.longbuf.d_block : ch.syncbuf.d_block);
+    if (!t0) return CWSLG_ERR_NO_FRAME;
+    hipSetDevice(c->device);
+    if (start_epoch) *start_epoch = t0;
+    if (long_list) s = RecSource{ch.longbuf.w.cand, ch.longbuf.w.ncand, nullptr, long_list == CWSLG_LIST_WSPR ? (int)WSPR_MAXCAND : (int)F4W_MAXCAND};
+    else s = RecSource{record_array(ch.syncbuf, k), ch.syncbuf.d_ncand, ch.syncbuf.d_nrec, ch.syncbuf.max_cand};
+    return begin_result_fetch(c, ch, rf);
+}
+
+// Flat body: the count and min(max, cap) items in one synchronise, the first `count` of them handed out.
+int fetch_flat(cwslg_ctx *c, int ch_id, int k, int long_list, void *dst, size_t item, int max, int *n, uint64_t *start_epoch)
+{
+    if (!c || !n || (max > 0 && !dst)) return CWSLG_ERR_ARG;
+    *n = 0;
+    RecSource s;
+    ResultFetch rf;                     // ticket + lifetime, released when the copy is done or the call fails
+    const int rc = fetch_begin(c, ch_id, k, long_list, start_epoch, s, rf);
+    if (rc) return rc;
+    // no context lock from here on
+    const int lim = std::min(std::max(max, 0), s.cap);
+    int cnt = 0;
+    std::vector<char> tmp((size_t)lim * item);
+    HIPCHK(c, hipStreamWaitEvent(rf.fs, rf.ev, 0));
+    HIPCHK(c, hipMemcpyAsync(&cnt, s.cnt, sizeof(int), hipMemcpyDeviceToHost, rf.fs));
+    if (lim > 0) HIPCHK(c, hipMemcpyAsync(tmp.data(), s.rec, tmp.size(), hipMemcpyDeviceToHost, rf.fs));
+    HIPCHK(c, hipStreamSynchronize(rf.fs));
+    cnt = std::max(0, std::min(cnt, lim));
+    if (cnt > 0) std::memcpy(dst, tmp.data(), (size_t)cnt * item);
+    *n = cnt;
+    return CWSLG_OK;
+}
+
+// The FT4 chain's slot layout rec[cnt][3] with nrec[k] records of candidate k, compacted in candidate order, then segment order (entry q of one
+// kind belongs to entry q of every other).  At most `max` items are written; the return value counts them all.
+int compact_records(void *dst, size_t item, int max, const int *nrec, const char *rec, int cnt)
+{
+    int out = 0;
+    for (int k = 0; k < cnt; ++k)
+        for (int q = 0; q < nrec[k] && q < 3; ++q) {
+            if (out < max) std::memcpy((char *)dst + (size_t)out * item, rec + ((size_t)k * 3 + q) * item, item);
+            ++out;
+        }
+    return out;
+}
+
+// Walk body: the count, synchronise, then nrec[count] and rec[count][3], synchronise, compacted.  An empty list is CWSLG_OK with the epoch set
+// and no second copy.
+int fetch_walk(cwslg_ctx *c, int ch_id, int k, void *dst, size_t item, int max, int *n, uint64_t *start_epoch)
+{
+    if (!c || !n || (max > 0 && !dst)) return CWSLG_ERR_ARG;
+    *n = 0;
+    RecSource s;
+    ResultFetch rf;
+    const int rc = fetch_begin(c, ch_id, k, 0, start_epoch, s, rf);
+    if (rc) return rc;
+    int cnt = 0;
+    HIPCHK(c, hipStreamWaitEvent(rf.fs, rf.ev, 0));
+    HIPCHK(c, hipMemcpyAsync(&cnt, s.cnt, sizeof(int), hipMemcpyDeviceToHost, rf.fs));
+    HIPCHK(c, hipStreamSynchronize(rf.fs));
+    cnt = std::max(0, std::min(cnt, s.cap));
+    if (cnt <= 0) return CWSLG_OK;
+    std::vector<int> nrec((size_t)cnt);
+    std::vector<char> rec((size_t)cnt * 3 * item);
+    HIPCHK(c, hipMemcpyAsync(nrec.data(), s.nrec, nrec.size() * sizeof(int), hipMemcpyDeviceToHost, rf.fs));
+    HIPCHK(c, hipMemcpyAsync(rec.data(), s.rec, rec.size(), hipMemcpyDeviceToHost, rf.fs));
+    HIPCHK(c, hipStreamSynchronize(rf.fs));
+    *n = std::min(compact_records(dst, item, max, nrec.data(), rec.data(), cnt), max);
+    return CWSLG_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -583,18 +676,12 @@ int cwslg_enable_sync(cwslg_ctx *c, int enable, float syncmin, int max_cand, int
         if (cfg.ib + 12 > FT8_NH1) cfg.ib = FT8_NH1 - 12;
         if (cfg.ib < cfg.ia) return fail(c, CWSLG_ERR_ARG, "empty sync frequency range");
         cfg.nbins = (cfg.ib + 13 + 31) / 32 * 32;   // row pitch = whole 128-byte lines (ft8_sync_chan_kernel fetches one line per band and step)
-        cfg.ft8_soft = c->sync_cfg.ft8_soft;
-        cfg.ft4_soft = c->sync_cfg.ft4_soft;
-        cfg.ft8_decode = c->sync_cfg.ft8_decode; cfg.ldpc_max_iter = c->sync_cfg.ldpc_max_iter; cfg.ldpc_min_nsync = c->sync_cfg.ldpc_min_nsync;
-        cfg.ft8_osd = c->sync_cfg.ft8_osd; cfg.osd_order = c->sync_cfg.osd_order; cfg.osd_min_nsync = c->sync_cfg.osd_min_nsync;
-        cfg.ft4_decode = c->sync_cfg.ft4_decode; cfg.ldpc4_max_iter = c->sync_cfg.ldpc4_max_iter; cfg.ldpc4_min_nsync = c->sync_cfg.ldpc4_min_nsync;
-        cfg.ldpc4_min_nqual = c->sync_cfg.ldpc4_min_nqual;
-        cfg.ft4_osd = c->sync_cfg.ft4_osd; cfg.osd4_order = c->sync_cfg.osd4_order; cfg.osd4_min_nsync = c->sync_cfg.osd4_min_nsync;
-        cfg.osd4_min_nqual = c->sync_cfg.osd4_min_nqual;
-        if (cfg.ft8_soft) cfg.nbins = (cfg.ib + 15 + 31) / 32 * 32;   // soft bits on: tone 7 of bin ib (ib + 14) lies inside the row
+        // the chains' settings, the coherent stage and the list order survive a re-enable.  syncmin_ft4 does NOT: it falls back to its default,
+        // and every caller sets it again behind this call ("cwslg_enable_sync starts from the default threshold": tests/test_gpu_ft4_decode.py,
+        // test_gpu_ft4_osd.py, test_gpu_record_fetch_races.py)
+        cfg.kept = c->sync_cfg.kept;
+        if (cfg.kept.ft8_soft) cfg.nbins = (cfg.ib + 15 + 31) / 32 * 32;   // soft bits on: tone 7 of bin ib (ib + 14) lies inside the row
         hipSetDevice(c->device);
-        cfg.ft4_coherent = c->sync_cfg.ft4_coherent;
-        cfg.order = c->sync_cfg.order;
         const int rc = sync_ensure_shared(c);             // the stage is enabled only with its tables in place
         if (rc) { c->sync_cfg.enabled = false; return rc; }
         c->sync_cfg = cfg;
@@ -608,7 +695,7 @@ int cwslg_set_candidate_order(cwslg_ctx *c, int order)
 {
     if (!c || (order != CWSLG_ORDER_SYNC_DESC && order != CWSLG_ORDER_FREQ_ASC)) return CWSLG_ERR_ARG;
     std::lock_guard<std::mutex> g(c->mu);
-    c->sync_cfg.order = order;
+    c->sync_cfg.kept.order = order;
     return CWSLG_OK;
 }
 
@@ -620,44 +707,15 @@ int cwslg_set_ft4_syncmin(cwslg_ctx *c, float syncmin)
     return CWSLG_OK;
 }
 
-// The candidate fetches hand a list out the way cwslg_fetch_frame hands a frame out (ABI 5): under the context mutex only the pointers are read
-// and a ticket of the channel's group is taken; the copies run on a fetch stream behind the group's generation event with the mutex released
-// (a list fetch during a 30 ms demod launch no longer blocks every pusher), and the group's next boundary -- the next writer of the buffers --
-// waits for the ticket.  *start_epoch is the start epoch of the frame the list was computed from.
+// The list of an FT8 or FT4 channel; it survives a boundary that ran with the stage disabled, under its own epoch.
 int cwslg_fetch_candidates(cwslg_ctx *c, int ch_id, cwslg_candidate *dst, int max, int *n, uint64_t *start_epoch)
 {
-    if (!c || !n || (max > 0 && !dst)) return CWSLG_ERR_ARG;
-    *n = 0;
-    const SyncChannelBuffers::Cand *src = nullptr;
-    const int *cnt_src = nullptr;
-    int lim = 0;
-    ResultFetch rf;
-    {
-        std::lock_guard<std::mutex> g(c->mu);
-        if (ch_id < 0 || ch_id >= (int)c->chans.size() || !c->chans[ch_id].open) return fail(c, CWSLG_ERR_ARG, "bad channel id");
-        Channel &ch = c->chans[ch_id];
-        if (!ch.have_frame || !ch.syncbuf.d_block || !ch.cand_t0) return CWSLG_ERR_NO_FRAME;
-        hipSetDevice(c->device);
-        if (start_epoch) *start_epoch = ch.cand_t0;
-        src = ch.syncbuf.d_cand; cnt_src = ch.syncbuf.d_ncand; lim = std::min(std::max(max, 0), ch.syncbuf.max_cand);
-        int rc = begin_result_fetch(c, ch, rf);
-        if (rc) return rc;
-    }
     static_assert(sizeof(cwslg_candidate) == sizeof(SyncChannelBuffers::Cand), "candidate layout");
-    int cnt = 0;
-    std::vector<SyncChannelBuffers::Cand> tmp((size_t)lim);
-    HIPCHK(c, hipStreamWaitEvent(rf.fs, rf.ev, 0));
-    HIPCHK(c, hipMemcpyAsync(&cnt, cnt_src, sizeof(int), hipMemcpyDeviceToHost, rf.fs));
-    if (lim > 0) HIPCHK(c, hipMemcpyAsync(tmp.data(), src, (size_t)lim * sizeof(cwslg_candidate), hipMemcpyDeviceToHost, rf.fs));
-    HIPCHK(c, hipStreamSynchronize(rf.fs));
-    cnt = std::max(0, std::min(cnt, lim));
-    if (cnt > 0) std::memcpy(dst, tmp.data(), (size_t)cnt * sizeof(cwslg_candidate));
-    *n = cnt;
-    return CWSLG_OK;
+    return fetch_flat(c, ch_id, REC_CAND, 0, dst, sizeof(cwslg_candidate), max, n, start_epoch);
 }
 
 // FT8 soft bits (ft8soft_kernels.hpp).  The records are handed out like the lists, and only together with them: a fetch needs the records, the
-// list and the frame to be of ONE epoch (soft_t0 == cand_t0 == frame_t0) -- after a boundary that ran with the feature off there is nothing to
+// list and the frame to be of ONE epoch (the REC_SOFT8 row of record_kinds.hpp) -- after a boundary that ran with the feature off there is nothing to
 // fetch, never an older slot's records under the newer epoch.
 int cwslg_enable_ft8_softbits(cwslg_ctx *c, int enable)
 {
@@ -665,44 +723,16 @@ int cwslg_enable_ft8_softbits(cwslg_ctx *c, int enable)
     std::lock_guard<std::mutex> g(c->mu);
     if (enable && !c->sync_cfg.enabled) return fail(c, CWSLG_ERR_ARG, "FT8 soft bits need the sync stage (cwslg_enable_sync)");
     SyncConfig &cfg = c->sync_cfg;
-    cfg.ft8_soft = enable != 0;
+    cfg.kept.ft8_soft = enable != 0;
     // the row pitch: ib + 13 as ever while the feature is off; ib + 15 while it is on (channels reallocate at their next boundary)
-    cfg.nbins = (cfg.ib + (cfg.ft8_soft ? 15 : 13) + 31) / 32 * 32;
+    cfg.nbins = (cfg.ib + (cfg.kept.ft8_soft ? 15 : 13) + 31) / 32 * 32;
     return CWSLG_OK;
 }
 
 int cwslg_fetch_ft8_softbits(cwslg_ctx *c, int ch_id, cwslg_ft8_soft *dst, int max, int *n, uint64_t *start_epoch)
 {
-    if (!c || !n || (max > 0 && !dst)) return CWSLG_ERR_ARG;
-    *n = 0;
-    const Ft8SoftRec *src = nullptr;
-    const int *cnt_src = nullptr;
-    int lim = 0;
-    ResultFetch rf;
-    {
-        std::lock_guard<std::mutex> g(c->mu);
-        if (ch_id < 0 || ch_id >= (int)c->chans.size() || !c->chans[ch_id].open) return fail(c, CWSLG_ERR_ARG, "bad channel id");
-        Channel &ch = c->chans[ch_id];
-        if (!ch.sync_ft8) return fail(c, CWSLG_ERR_MODE, "soft bits exist for FT8 channels only (mode %s)", ch.mode.c_str());
-        if (!ch.have_frame || !ch.syncbuf.d_block || !ch.syncbuf.d_soft || !ch.soft_t0 || ch.soft_t0 != ch.frame_t0 || ch.soft_t0 != ch.cand_t0)
-            return CWSLG_ERR_NO_FRAME;
-        hipSetDevice(c->device);
-        if (start_epoch) *start_epoch = ch.soft_t0;
-        src = ch.syncbuf.d_soft; cnt_src = ch.syncbuf.d_ncand; lim = std::min(std::max(max, 0), ch.syncbuf.max_cand);
-        int rc = begin_result_fetch(c, ch, rf);
-        if (rc) return rc;
-    }
     static_assert(sizeof(cwslg_ft8_soft) == sizeof(Ft8SoftRec), "record layout");
-    int cnt = 0;
-    std::vector<Ft8SoftRec> tmp((size_t)lim);
-    HIPCHK(c, hipStreamWaitEvent(rf.fs, rf.ev, 0));
-    HIPCHK(c, hipMemcpyAsync(&cnt, cnt_src, sizeof(int), hipMemcpyDeviceToHost, rf.fs));
-    if (lim > 0) HIPCHK(c, hipMemcpyAsync(tmp.data(), src, (size_t)lim * sizeof(Ft8SoftRec), hipMemcpyDeviceToHost, rf.fs));
-    HIPCHK(c, hipStreamSynchronize(rf.fs));
-    cnt = std::max(0, std::min(cnt, lim));
-    if (cnt > 0) std::memcpy(dst, tmp.data(), (size_t)cnt * sizeof(Ft8SoftRec));
-    *n = cnt;
-    return CWSLG_OK;
+    return fetch_flat(c, ch_id, REC_SOFT8, 0, dst, sizeof(cwslg_ft8_soft), max, n, start_epoch);
 }
 
 // The generator's device block exists from the first use of OSD on (while OSD has never been used a context holds no byte of it).
@@ -747,8 +777,8 @@ int cwslg_set_ldpc_code(cwslg_ctx *c, const uint8_t *nm)
         c->sync_shared.osd_ready = c->sync_shared.osd_dirty = true;
         if (c->sync_shared.d_osdgen) HIPCHK(c, osd_upload_gen(c));      // (the streams are drained: no queued OSD launch still reads the old block)
     } else {
-        c->sync_cfg.ft8_osd = false;
-        c->sync_cfg.ft4_osd = false;
+        c->sync_cfg.kept.ft8_osd = false;
+        c->sync_cfg.kept.ft4_osd = false;
     }
     return CWSLG_OK;
 }
@@ -758,48 +788,19 @@ int cwslg_enable_ft8_decode(cwslg_ctx *c, int enable, int max_iter, int min_nsyn
     if (!c) return CWSLG_ERR_ARG;
     std::lock_guard<std::mutex> g(c->mu);
     SyncConfig &cfg = c->sync_cfg;
-    if (!enable) { cfg.ft8_decode = false; return CWSLG_OK; }
+    if (!enable) { cfg.kept.ft8_decode = false; return CWSLG_OK; }
     if (max_iter < 1 || max_iter > 200 || min_nsync < 0 || min_nsync > 22) return fail(c, CWSLG_ERR_ARG, "FT8 decode parameters out of range");
     if (!c->sync_shared.ldpc_loaded) return fail(c, CWSLG_ERR_ARG, "FT8 decode needs a parity-check table (cwslg_set_ldpc_code)");
-    if (!cfg.enabled || !cfg.ft8_soft) return fail(c, CWSLG_ERR_ARG, "FT8 decode needs the sync stage and FT8 soft bits (cwslg_enable_sync, cwslg_enable_ft8_softbits)");
-    cfg.ft8_decode = true; cfg.ldpc_max_iter = max_iter; cfg.ldpc_min_nsync = min_nsync;
+    if (!cfg.enabled || !cfg.kept.ft8_soft) return fail(c, CWSLG_ERR_ARG, "FT8 decode needs the sync stage and FT8 soft bits (cwslg_enable_sync, cwslg_enable_ft8_softbits)");
+    cfg.kept.ft8_decode = true; cfg.kept.ldpc_max_iter = max_iter; cfg.kept.ldpc_min_nsync = min_nsync;
     return CWSLG_OK;
 }
 
 // Handed out like the soft-bit records, and only together with them: decode records, soft-bit records, list and frame of ONE epoch.
 int cwslg_fetch_ft8_decode(cwslg_ctx *c, int ch_id, cwslg_ft8_msg *dst, int max, int *n, uint64_t *start_epoch)
 {
-    if (!c || !n || (max > 0 && !dst)) return CWSLG_ERR_ARG;
-    *n = 0;
-    const Ft8MsgRec *src = nullptr;
-    const int *cnt_src = nullptr;
-    int lim = 0;
-    ResultFetch rf;
-    {
-        std::lock_guard<std::mutex> g(c->mu);
-        if (ch_id < 0 || ch_id >= (int)c->chans.size() || !c->chans[ch_id].open) return fail(c, CWSLG_ERR_ARG, "bad channel id");
-        Channel &ch = c->chans[ch_id];
-        if (!ch.sync_ft8) return fail(c, CWSLG_ERR_MODE, "decode records exist for FT8 channels only (mode %s)", ch.mode.c_str());
-        if (!ch.have_frame || !ch.syncbuf.d_block || !ch.syncbuf.d_msg || !ch.msg_t0 || ch.msg_t0 != ch.frame_t0 || ch.msg_t0 != ch.cand_t0 ||
-            ch.msg_t0 != ch.soft_t0)
-            return CWSLG_ERR_NO_FRAME;
-        hipSetDevice(c->device);
-        if (start_epoch) *start_epoch = ch.msg_t0;
-        src = ch.syncbuf.d_msg; cnt_src = ch.syncbuf.d_ncand; lim = std::min(std::max(max, 0), ch.syncbuf.max_cand);
-        int rc = begin_result_fetch(c, ch, rf);
-        if (rc) return rc;
-    }
     static_assert(sizeof(cwslg_ft8_msg) == sizeof(Ft8MsgRec), "record layout");
-    int cnt = 0;
-    std::vector<Ft8MsgRec> tmp((size_t)lim);
-    HIPCHK(c, hipStreamWaitEvent(rf.fs, rf.ev, 0));
-    HIPCHK(c, hipMemcpyAsync(&cnt, cnt_src, sizeof(int), hipMemcpyDeviceToHost, rf.fs));
-    if (lim > 0) HIPCHK(c, hipMemcpyAsync(tmp.data(), src, (size_t)lim * sizeof(Ft8MsgRec), hipMemcpyDeviceToHost, rf.fs));
-    HIPCHK(c, hipStreamSynchronize(rf.fs));
-    cnt = std::max(0, std::min(cnt, lim));
-    if (cnt > 0) std::memcpy(dst, tmp.data(), (size_t)cnt * sizeof(Ft8MsgRec));
-    *n = cnt;
-    return CWSLG_OK;
+    return fetch_flat(c, ch_id, REC_MSG8, 0, dst, sizeof(cwslg_ft8_msg), max, n, start_epoch);
 }
 
 // The same kernel on n sets of 174 metrics from host memory, no nsync filter; synchronous (temporary device buffers, the context's stream).
@@ -833,49 +834,20 @@ int cwslg_enable_ft8_osd(cwslg_ctx *c, int enable, int order, int min_nsync)
     if (!c) return CWSLG_ERR_ARG;
     std::lock_guard<std::mutex> g(c->mu);
     SyncConfig &cfg = c->sync_cfg;
-    if (!enable) { cfg.ft8_osd = false; return CWSLG_OK; }
+    if (!enable) { cfg.kept.ft8_osd = false; return CWSLG_OK; }
     if (order < 0 || order > 2 || min_nsync < 0 || min_nsync > 22) return fail(c, CWSLG_ERR_ARG, "FT8 OSD parameters out of range");
     if (!c->sync_shared.osd_ready) return fail(c, CWSLG_ERR_ARG, "FT8 OSD needs a parity-check table of rank 83 (cwslg_set_ldpc_code)");
     hipSetDevice(c->device);
     HIPCHK(c, osd_upload_gen(c));
-    cfg.ft8_osd = true; cfg.osd_order = order; cfg.osd_min_nsync = min_nsync;
+    cfg.kept.ft8_osd = true; cfg.kept.osd_order = order; cfg.kept.osd_min_nsync = min_nsync;
     return CWSLG_OK;
 }
 
 // Handed out like the decode records, and only together with them: OSD, decode and soft-bit records, list and frame of ONE epoch.
 int cwslg_fetch_ft8_osd(cwslg_ctx *c, int ch_id, cwslg_osd_msg *dst, int max, int *n, uint64_t *start_epoch)
 {
-    if (!c || !n || (max > 0 && !dst)) return CWSLG_ERR_ARG;
-    *n = 0;
-    const OsdRec *src = nullptr;
-    const int *cnt_src = nullptr;
-    int lim = 0;
-    ResultFetch rf;
-    {
-        std::lock_guard<std::mutex> g(c->mu);
-        if (ch_id < 0 || ch_id >= (int)c->chans.size() || !c->chans[ch_id].open) return fail(c, CWSLG_ERR_ARG, "bad channel id");
-        Channel &ch = c->chans[ch_id];
-        if (!ch.sync_ft8) return fail(c, CWSLG_ERR_MODE, "OSD records exist for FT8 channels only (mode %s)", ch.mode.c_str());
-        if (!ch.have_frame || !ch.syncbuf.d_block || !ch.syncbuf.d_osd || !ch.osd_t0 || ch.osd_t0 != ch.frame_t0 || ch.osd_t0 != ch.cand_t0 ||
-            ch.osd_t0 != ch.soft_t0 || ch.osd_t0 != ch.msg_t0)
-            return CWSLG_ERR_NO_FRAME;
-        hipSetDevice(c->device);
-        if (start_epoch) *start_epoch = ch.osd_t0;
-        src = ch.syncbuf.d_osd; cnt_src = ch.syncbuf.d_ncand; lim = std::min(std::max(max, 0), ch.syncbuf.max_cand);
-        int rc = begin_result_fetch(c, ch, rf);
-        if (rc) return rc;
-    }
     static_assert(sizeof(cwslg_osd_msg) == sizeof(OsdRec), "record layout");
-    int cnt = 0;
-    std::vector<OsdRec> tmp((size_t)lim);
-    HIPCHK(c, hipStreamWaitEvent(rf.fs, rf.ev, 0));
-    HIPCHK(c, hipMemcpyAsync(&cnt, cnt_src, sizeof(int), hipMemcpyDeviceToHost, rf.fs));
-    if (lim > 0) HIPCHK(c, hipMemcpyAsync(tmp.data(), src, (size_t)lim * sizeof(OsdRec), hipMemcpyDeviceToHost, rf.fs));
-    HIPCHK(c, hipStreamSynchronize(rf.fs));
-    cnt = std::max(0, std::min(cnt, lim));
-    if (cnt > 0) std::memcpy(dst, tmp.data(), (size_t)cnt * sizeof(OsdRec));
-    *n = cnt;
-    return CWSLG_OK;
+    return fetch_flat(c, ch_id, REC_OSD8, 0, dst, sizeof(cwslg_osd_msg), max, n, start_epoch);
 }
 
 // The same kernel on n sets of 174 metrics from host memory, no gates; synchronous (temporary device buffers, the context's stream).
@@ -908,108 +880,33 @@ int cwslg_enable_ft4_coherent(cwslg_ctx *c, int enable)
 {
     if (!c) return CWSLG_ERR_ARG;
     std::lock_guard<std::mutex> g(c->mu);
-    c->sync_cfg.ft4_coherent = enable != 0;
+    c->sync_cfg.kept.ft4_coherent = enable != 0;
     return CWSLG_OK;
 }
 
 int cwslg_fetch_ft4_sync(cwslg_ctx *c, int ch_id, cwslg_ft4_sync *dst, int max, int *n, uint64_t *start_epoch)
 {
-    if (!c || !n || (max > 0 && !dst)) return CWSLG_ERR_ARG;
-    *n = 0;
-    const int *cnt_src = nullptr, *nrec_src = nullptr;
-    const char *rec_src = nullptr;
-    int lim = 0;
-    ResultFetch rf;
-    {
-        std::lock_guard<std::mutex> g(c->mu);
-        if (ch_id < 0 || ch_id >= (int)c->chans.size() || !c->chans[ch_id].open) return fail(c, CWSLG_ERR_ARG, "bad channel id");
-        Channel &ch = c->chans[ch_id];
-        // the records are walked under the list's count: both must be of ONE epoch (after a boundary that ran with the coherent stage off the
-        // list is new and d_rec / d_nrec are the older slot's -- nothing to fetch, never those records under the newer epoch)
-        if (!ch.have_frame || !ch.syncbuf.d_block || !ch.syncbuf.d_ft4c || !ch.ft4c_t0 || ch.ft4c_t0 != ch.cand_t0) return CWSLG_ERR_NO_FRAME;
-        hipSetDevice(c->device);
-        if (start_epoch) *start_epoch = ch.ft4c_t0;
-        cnt_src = ch.syncbuf.d_ncand; nrec_src = ch.syncbuf.d_nrec; rec_src = (const char *)ch.syncbuf.d_rec; lim = ch.syncbuf.max_cand;
-        int rc = begin_result_fetch(c, ch, rf);
-        if (rc) return rc;
-    }
     static_assert(sizeof(cwslg_ft4_sync) == sizeof(Ft4Rec), "record layout");
-    int cnt = 0;
-    std::vector<int> nrec((size_t)lim);
-    std::vector<Ft4Rec> rec((size_t)lim * 3);
-    HIPCHK(c, hipStreamWaitEvent(rf.fs, rf.ev, 0));
-    HIPCHK(c, hipMemcpyAsync(&cnt, cnt_src, sizeof(int), hipMemcpyDeviceToHost, rf.fs));
-    HIPCHK(c, hipStreamSynchronize(rf.fs));
-    cnt = std::max(0, std::min(cnt, lim));
-    if (cnt <= 0) return CWSLG_OK;
-    HIPCHK(c, hipMemcpyAsync(nrec.data(), nrec_src, (size_t)cnt * sizeof(int), hipMemcpyDeviceToHost, rf.fs));
-    HIPCHK(c, hipMemcpyAsync(rec.data(), rec_src, (size_t)cnt * 3 * sizeof(Ft4Rec), hipMemcpyDeviceToHost, rf.fs));
-    HIPCHK(c, hipStreamSynchronize(rf.fs));
-    int out = 0;
-    for (int k = 0; k < cnt; ++k)                               // candidate order, then segment order
-        for (int q = 0; q < nrec[k] && q < 3; ++q) {
-            if (out < max) std::memcpy(&dst[out], &rec[(size_t)k * 3 + q], sizeof(Ft4Rec));
-            ++out;
-        }
-    *n = std::min(out, max);
-    return CWSLG_OK;
+    return fetch_walk(c, ch_id, REC_FT4SYNC, dst, sizeof(cwslg_ft4_sync), max, n, start_epoch);
 }
 
 // FT4 soft bits (ft4soft_kernels.hpp).  One record per cwslg_ft4_sync record, compacted from the slot layout by the same nrec walk as
-// cwslg_fetch_ft4_sync; handed out only when soft records, sync records, list and frame are of ONE epoch (soft4_t0 == cand_t0 == frame_t0: the
-// launch that sets soft4_t0 runs behind the refinement of the same boundary) -- after a boundary that ran with the feature or the coherent stage
+// cwslg_fetch_ft4_sync; handed out only when soft records, sync records, list and frame are of ONE epoch (the REC_SOFT4 row of record_kinds.hpp: the
+// launch that sets its stamp runs behind the refinement of the same boundary) -- after a boundary that ran with the feature or the coherent stage
 // off there is nothing to fetch, never an older slot's records under the newer epoch.
 int cwslg_enable_ft4_softbits(cwslg_ctx *c, int enable)
 {
     if (!c) return CWSLG_ERR_ARG;
     std::lock_guard<std::mutex> g(c->mu);
     if (enable && !c->sync_cfg.enabled) return fail(c, CWSLG_ERR_ARG, "FT4 soft bits need the sync stage (cwslg_enable_sync)");
-    c->sync_cfg.ft4_soft = enable != 0;
+    c->sync_cfg.kept.ft4_soft = enable != 0;
     return CWSLG_OK;
 }
 
 int cwslg_fetch_ft4_softbits(cwslg_ctx *c, int ch_id, cwslg_ft4_soft *dst, int max, int *n, uint64_t *start_epoch)
 {
-    if (!c || !n || (max > 0 && !dst)) return CWSLG_ERR_ARG;
-    *n = 0;
-    const int *cnt_src = nullptr, *nrec_src = nullptr;
-    const Ft4SoftRec *rec_src = nullptr;
-    int lim = 0;
-    ResultFetch rf;
-    {
-        std::lock_guard<std::mutex> g(c->mu);
-        if (ch_id < 0 || ch_id >= (int)c->chans.size() || !c->chans[ch_id].open) return fail(c, CWSLG_ERR_ARG, "bad channel id");
-        Channel &ch = c->chans[ch_id];
-        if (!ch.sync_ft4) return fail(c, CWSLG_ERR_MODE, "FT4 soft bits exist for FT4 channels only (mode %s)", ch.mode.c_str());
-        if (!ch.have_frame || !ch.syncbuf.d_block || !ch.syncbuf.d_ft4c || !ch.syncbuf.d_ft4soft || !ch.soft4_t0 || ch.soft4_t0 != ch.frame_t0 ||
-            ch.soft4_t0 != ch.cand_t0)
-            return CWSLG_ERR_NO_FRAME;
-        hipSetDevice(c->device);
-        if (start_epoch) *start_epoch = ch.soft4_t0;
-        cnt_src = ch.syncbuf.d_ncand; nrec_src = ch.syncbuf.d_nrec; rec_src = ch.syncbuf.d_ft4soft; lim = ch.syncbuf.max_cand;
-        int rc = begin_result_fetch(c, ch, rf);
-        if (rc) return rc;
-    }
     static_assert(sizeof(cwslg_ft4_soft) == sizeof(Ft4SoftRec), "record layout");
-    int cnt = 0;
-    HIPCHK(c, hipStreamWaitEvent(rf.fs, rf.ev, 0));
-    HIPCHK(c, hipMemcpyAsync(&cnt, cnt_src, sizeof(int), hipMemcpyDeviceToHost, rf.fs));
-    HIPCHK(c, hipStreamSynchronize(rf.fs));
-    cnt = std::max(0, std::min(cnt, lim));
-    if (cnt <= 0) return CWSLG_OK;
-    std::vector<int> nrec((size_t)cnt);
-    std::vector<Ft4SoftRec> rec((size_t)cnt * 3);
-    HIPCHK(c, hipMemcpyAsync(nrec.data(), nrec_src, (size_t)cnt * sizeof(int), hipMemcpyDeviceToHost, rf.fs));
-    HIPCHK(c, hipMemcpyAsync(rec.data(), rec_src, (size_t)cnt * 3 * sizeof(Ft4SoftRec), hipMemcpyDeviceToHost, rf.fs));
-    HIPCHK(c, hipStreamSynchronize(rf.fs));
-    int out = 0;
-    for (int k = 0; k < cnt; ++k)                               // candidate order, then segment order: entry q of cwslg_fetch_ft4_sync
-        for (int q = 0; q < nrec[k] && q < 3; ++q) {
-            if (out < max) std::memcpy(&dst[out], &rec[(size_t)k * 3 + q], sizeof(Ft4SoftRec));
-            ++out;
-        }
-    *n = std::min(out, max);
-    return CWSLG_OK;
+    return fetch_walk(c, ch_id, REC_SOFT4, dst, sizeof(cwslg_ft4_soft), max, n, start_epoch);
 }
 
 // FT4 decode (ldpc_kernels.hpp's third addressing mode): the FT8 decode's rules with the FT4 soft bits in the place of the FT8 ones.
@@ -1018,12 +915,12 @@ int cwslg_enable_ft4_decode(cwslg_ctx *c, int enable, int max_iter, int min_nsyn
     if (!c) return CWSLG_ERR_ARG;
     std::lock_guard<std::mutex> g(c->mu);
     SyncConfig &cfg = c->sync_cfg;
-    if (!enable) { cfg.ft4_decode = false; return CWSLG_OK; }
+    if (!enable) { cfg.kept.ft4_decode = false; return CWSLG_OK; }
     if (max_iter < 1 || max_iter > 200 || min_nsync < 0 || min_nsync > 17 || min_nqual < 0 || min_nqual > 33)
         return fail(c, CWSLG_ERR_ARG, "FT4 decode parameters out of range");
     if (!c->sync_shared.ldpc_loaded) return fail(c, CWSLG_ERR_ARG, "FT4 decode needs a parity-check table (cwslg_set_ldpc_code)");
-    if (!cfg.enabled || !cfg.ft4_soft) return fail(c, CWSLG_ERR_ARG, "FT4 decode needs the sync stage and FT4 soft bits (cwslg_enable_sync, cwslg_enable_ft4_softbits)");
-    cfg.ft4_decode = true; cfg.ldpc4_max_iter = max_iter; cfg.ldpc4_min_nsync = min_nsync; cfg.ldpc4_min_nqual = min_nqual;
+    if (!cfg.enabled || !cfg.kept.ft4_soft) return fail(c, CWSLG_ERR_ARG, "FT4 decode needs the sync stage and FT4 soft bits (cwslg_enable_sync, cwslg_enable_ft4_softbits)");
+    cfg.kept.ft4_decode = true; cfg.kept.ldpc4_max_iter = max_iter; cfg.kept.ldpc4_min_nsync = min_nsync; cfg.kept.ldpc4_min_nqual = min_nqual;
     return CWSLG_OK;
 }
 
@@ -1031,46 +928,8 @@ int cwslg_enable_ft4_decode(cwslg_ctx *c, int enable, int max_iter, int min_nsyn
 // records, sync records, list and frame of ONE epoch.
 int cwslg_fetch_ft4_decode(cwslg_ctx *c, int ch_id, cwslg_ft4_msg *dst, int max, int *n, uint64_t *start_epoch)
 {
-    if (!c || !n || (max > 0 && !dst)) return CWSLG_ERR_ARG;
-    *n = 0;
-    const int *cnt_src = nullptr, *nrec_src = nullptr;
-    const Ft4MsgRec *rec_src = nullptr;
-    int lim = 0;
-    ResultFetch rf;
-    {
-        std::lock_guard<std::mutex> g(c->mu);
-        if (ch_id < 0 || ch_id >= (int)c->chans.size() || !c->chans[ch_id].open) return fail(c, CWSLG_ERR_ARG, "bad channel id");
-        Channel &ch = c->chans[ch_id];
-        if (!ch.sync_ft4) return fail(c, CWSLG_ERR_MODE, "FT4 decode records exist for FT4 channels only (mode %s)", ch.mode.c_str());
-        if (!ch.have_frame || !ch.syncbuf.d_block || !ch.syncbuf.d_ft4c || !ch.syncbuf.d_ft4soft || !ch.syncbuf.d_ft4msg || !ch.msg4_t0 ||
-            ch.msg4_t0 != ch.frame_t0 || ch.msg4_t0 != ch.cand_t0 || ch.msg4_t0 != ch.soft4_t0)
-            return CWSLG_ERR_NO_FRAME;
-        hipSetDevice(c->device);
-        if (start_epoch) *start_epoch = ch.msg4_t0;
-        cnt_src = ch.syncbuf.d_ncand; nrec_src = ch.syncbuf.d_nrec; rec_src = ch.syncbuf.d_ft4msg; lim = ch.syncbuf.max_cand;
-        int rc = begin_result_fetch(c, ch, rf);
-        if (rc) return rc;
-    }
     static_assert(sizeof(cwslg_ft4_msg) == sizeof(Ft4MsgRec), "record layout");
-    int cnt = 0;
-    HIPCHK(c, hipStreamWaitEvent(rf.fs, rf.ev, 0));
-    HIPCHK(c, hipMemcpyAsync(&cnt, cnt_src, sizeof(int), hipMemcpyDeviceToHost, rf.fs));
-    HIPCHK(c, hipStreamSynchronize(rf.fs));
-    cnt = std::max(0, std::min(cnt, lim));
-    if (cnt <= 0) return CWSLG_OK;
-    std::vector<int> nrec((size_t)cnt);
-    std::vector<Ft4MsgRec> rec((size_t)cnt * 3);
-    HIPCHK(c, hipMemcpyAsync(nrec.data(), nrec_src, (size_t)cnt * sizeof(int), hipMemcpyDeviceToHost, rf.fs));
-    HIPCHK(c, hipMemcpyAsync(rec.data(), rec_src, (size_t)cnt * 3 * sizeof(Ft4MsgRec), hipMemcpyDeviceToHost, rf.fs));
-    HIPCHK(c, hipStreamSynchronize(rf.fs));
-    int out = 0;
-    for (int k = 0; k < cnt; ++k)                               // candidate order, then segment order: entry q of cwslg_fetch_ft4_sync
-        for (int q = 0; q < nrec[k] && q < 3; ++q) {
-            if (out < max) std::memcpy(&dst[out], &rec[(size_t)k * 3 + q], sizeof(Ft4MsgRec));
-            ++out;
-        }
-    *n = std::min(out, max);
-    return CWSLG_OK;
+    return fetch_walk(c, ch_id, REC_MSG4, dst, sizeof(cwslg_ft4_msg), max, n, start_epoch);
 }
 
 // FT4 OSD (osd_kernels.hpp's third addressing mode): one launch behind the FT4 decode launch, on the sets of the records no set of which BP
@@ -1080,13 +939,13 @@ int cwslg_enable_ft4_osd(cwslg_ctx *c, int enable, int order, int min_nsync, int
     if (!c) return CWSLG_ERR_ARG;
     std::lock_guard<std::mutex> g(c->mu);
     SyncConfig &cfg = c->sync_cfg;
-    if (!enable) { cfg.ft4_osd = false; return CWSLG_OK; }
+    if (!enable) { cfg.kept.ft4_osd = false; return CWSLG_OK; }
     if (order < 0 || order > 2 || min_nsync < 0 || min_nsync > 17 || min_nqual < 0 || min_nqual > 33)
         return fail(c, CWSLG_ERR_ARG, "FT4 OSD parameters out of range");
     if (!c->sync_shared.osd_ready) return fail(c, CWSLG_ERR_ARG, "FT4 OSD needs a parity-check table of rank 83 (cwslg_set_ldpc_code)");
     hipSetDevice(c->device);
     HIPCHK(c, osd_upload_gen(c));
-    cfg.ft4_osd = true; cfg.osd4_order = order; cfg.osd4_min_nsync = min_nsync; cfg.osd4_min_nqual = min_nqual;
+    cfg.kept.ft4_osd = true; cfg.kept.osd4_order = order; cfg.kept.osd4_min_nsync = min_nsync; cfg.kept.osd4_min_nqual = min_nqual;
     return CWSLG_OK;
 }
 
@@ -1094,46 +953,8 @@ int cwslg_enable_ft4_osd(cwslg_ctx *c, int enable, int order, int min_nsync, int
 // records, sync records, list and frame of ONE epoch.
 int cwslg_fetch_ft4_osd(cwslg_ctx *c, int ch_id, cwslg_ft4_osd *dst, int max, int *n, uint64_t *start_epoch)
 {
-    if (!c || !n || (max > 0 && !dst)) return CWSLG_ERR_ARG;
-    *n = 0;
-    const int *cnt_src = nullptr, *nrec_src = nullptr;
-    const Ft4OsdRec *rec_src = nullptr;
-    int lim = 0;
-    ResultFetch rf;
-    {
-        std::lock_guard<std::mutex> g(c->mu);
-        if (ch_id < 0 || ch_id >= (int)c->chans.size() || !c->chans[ch_id].open) return fail(c, CWSLG_ERR_ARG, "bad channel id");
-        Channel &ch = c->chans[ch_id];
-        if (!ch.sync_ft4) return fail(c, CWSLG_ERR_MODE, "FT4 OSD records exist for FT4 channels only (mode %s)", ch.mode.c_str());
-        if (!ch.have_frame || !ch.syncbuf.d_block || !ch.syncbuf.d_ft4c || !ch.syncbuf.d_ft4soft || !ch.syncbuf.d_ft4msg || !ch.syncbuf.d_ft4osd ||
-            !ch.osd4_t0 || ch.osd4_t0 != ch.frame_t0 || ch.osd4_t0 != ch.cand_t0 || ch.osd4_t0 != ch.soft4_t0 || ch.osd4_t0 != ch.msg4_t0)
-            return CWSLG_ERR_NO_FRAME;
-        hipSetDevice(c->device);
-        if (start_epoch) *start_epoch = ch.osd4_t0;
-        cnt_src = ch.syncbuf.d_ncand; nrec_src = ch.syncbuf.d_nrec; rec_src = ch.syncbuf.d_ft4osd; lim = ch.syncbuf.max_cand;
-        int rc = begin_result_fetch(c, ch, rf);
-        if (rc) return rc;
-    }
     static_assert(sizeof(cwslg_ft4_osd) == sizeof(Ft4OsdRec), "record layout");
-    int cnt = 0;
-    HIPCHK(c, hipStreamWaitEvent(rf.fs, rf.ev, 0));
-    HIPCHK(c, hipMemcpyAsync(&cnt, cnt_src, sizeof(int), hipMemcpyDeviceToHost, rf.fs));
-    HIPCHK(c, hipStreamSynchronize(rf.fs));
-    cnt = std::max(0, std::min(cnt, lim));
-    if (cnt <= 0) return CWSLG_OK;
-    std::vector<int> nrec((size_t)cnt);
-    std::vector<Ft4OsdRec> rec((size_t)cnt * 3);
-    HIPCHK(c, hipMemcpyAsync(nrec.data(), nrec_src, (size_t)cnt * sizeof(int), hipMemcpyDeviceToHost, rf.fs));
-    HIPCHK(c, hipMemcpyAsync(rec.data(), rec_src, (size_t)cnt * 3 * sizeof(Ft4OsdRec), hipMemcpyDeviceToHost, rf.fs));
-    HIPCHK(c, hipStreamSynchronize(rf.fs));
-    int out = 0;
-    for (int k = 0; k < cnt; ++k)                               // candidate order, then segment order: entry q of cwslg_fetch_ft4_sync
-        for (int q = 0; q < nrec[k] && q < 3; ++q) {
-            if (out < max) std::memcpy(&dst[out], &rec[(size_t)k * 3 + q], sizeof(Ft4OsdRec));
-            ++out;
-        }
-    *n = std::min(out, max);
-    return CWSLG_OK;
+    return fetch_walk(c, ch_id, REC_OSD4, dst, sizeof(cwslg_ft4_osd), max, n, start_epoch);
 }
 
 int cwslg_sync_debug_fetch(cwslg_ctx *c, int ch_id, int what, void *dst, size_t cap_bytes, size_t *n_items, int *row_len)

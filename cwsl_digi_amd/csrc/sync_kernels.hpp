@@ -37,22 +37,26 @@ constexpr int SYNC_MAXPRE = 1000;       // MAXPRECAND of sync8.f90: pre-candidat
 struct SyncConfig {
     bool enabled = false;
     float syncmin = 1.5f;
-    float syncmin_ft4 = 1.2f;             // ft4_decode's threshold for getcandidates4
-    bool ft4_coherent = true;             // run ft4_downsample + sync4d on every FT4 candidate (ft4sync_kernels.hpp)
+    float syncmin_ft4 = 1.2f;             // ft4_decode's threshold for getcandidates4 (NOT kept by a re-enable, see cwslg_enable_sync)
     int max_cand = 200;
-    int order = 0;                        // cwslg_set_candidate_order: 0 strongest first (cut at max_cand in that order), 1 ascending frequency (cut in THAT order)
     int f_lo_hz = 200, f_hi_hz = 3000;
     int ia = 64, ib = 960, nbins = 976;   // derived: bin range and stored row length (ib+13 rounded up to 16)
-    bool ft4_soft = false;                // cwslg_enable_ft4_softbits: soft bits per refined FT4 sync record (ft4soft_kernels.hpp)
-    bool ft8_soft = false;                // cwslg_enable_ft8_softbits: soft bits per FT8 candidate (ft8soft_kernels.hpp); the row then holds tone 7 of bin ib (ib+15 rounded up)
-    bool ft8_decode = false;              // cwslg_enable_ft8_decode: LDPC(174,91) decode + CRC-14 per FT8 candidate (ldpc_kernels.hpp); runs only while ft8_soft is on too
-    int ldpc_max_iter = 30, ldpc_min_nsync = 7;
-    bool ft4_decode = false;              // cwslg_enable_ft4_decode: the same decode on the three metric sets of every FT4 soft-bit record; runs only while ft4_coherent and ft4_soft are on too
-    int ldpc4_max_iter = 30, ldpc4_min_nsync = 8, ldpc4_min_nqual = 20;
-    bool ft8_osd = false;                 // cwslg_enable_ft8_osd: ordered-statistics decoding of the candidates the FT8 decode attempted without crc_ok (osd_kernels.hpp); runs only while ft8_soft and ft8_decode are on too
-    int osd_order = 2, osd_min_nsync = 7;
-    bool ft4_osd = false;                 // cwslg_enable_ft4_osd: the same OSD on the sets of the FT4 records no set of which BP brought to crc_ok; runs only while ft4_coherent, ft4_soft and ft4_decode are on too
-    int osd4_order = 2, osd4_min_nsync = 8, osd4_min_nqual = 20;
+    // What a later cwslg_enable_sync carries over from the configuration in force, in one assignment: the decode chains' switches and
+    // parameters, the coherent stage's switch and the list order.  A new stage's settings belong here.
+    struct Kept {
+        bool ft4_coherent = true;         // run ft4_downsample + sync4d on every FT4 candidate (ft4sync_kernels.hpp)
+        int order = 0;                    // cwslg_set_candidate_order: 0 strongest first (cut at max_cand in that order), 1 ascending frequency (cut in THAT order)
+        bool ft4_soft = false;            // cwslg_enable_ft4_softbits: soft bits per refined FT4 sync record (ft4soft_kernels.hpp)
+        bool ft8_soft = false;            // cwslg_enable_ft8_softbits: soft bits per FT8 candidate (ft8soft_kernels.hpp); the row then holds tone 7 of bin ib (ib+15 rounded up)
+        bool ft8_decode = false;          // cwslg_enable_ft8_decode: LDPC(174,91) decode + CRC-14 per FT8 candidate (ldpc_kernels.hpp); runs only while ft8_soft is on too
+        int ldpc_max_iter = 30, ldpc_min_nsync = 7;
+        bool ft4_decode = false;          // cwslg_enable_ft4_decode: the same decode on the three metric sets of every FT4 soft-bit record; runs only while ft4_coherent and ft4_soft are on too
+        int ldpc4_max_iter = 30, ldpc4_min_nsync = 8, ldpc4_min_nqual = 20;
+        bool ft8_osd = false;             // cwslg_enable_ft8_osd: ordered-statistics decoding of the candidates the FT8 decode attempted without crc_ok (osd_kernels.hpp); runs only while ft8_soft and ft8_decode are on too
+        int osd_order = 2, osd_min_nsync = 7;
+        bool ft4_osd = false;             // cwslg_enable_ft4_osd: the same OSD on the sets of the FT4 records no set of which BP brought to crc_ok; runs only while ft4_coherent, ft4_soft and ft4_decode are on too
+        int osd4_order = 2, osd4_min_nsync = 8, osd4_min_nqual = 20;
+    } kept;
 };
 
 struct SyncTables {                       // device pointers: W_NZ, W_128, 0.5 W_2NZ twiddles, optional window

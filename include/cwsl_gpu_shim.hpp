@@ -222,87 +222,31 @@ public:
     }
     // FT4 channels: every candidate refined coherently (start sample, frequency tweak, sync) -- cwslg_fetch_ft4_sync
     int ft4Sync(std::vector<cwslg_ft4_sync> &out, int max = 1800)
-    {
-        out.resize(max);
-        int n = 0;
-        const int rc = cwslg_fetch_ft4_sync(ctx_.raw(), id_, out.data(), max, &n, nullptr);
-        if (rc == CWSLG_ERR_NO_FRAME) { out.clear(); return 0; }
-        check(ctx_.raw(), rc);
-        out.resize(n);
-        return n;
-    }
+    { return fetchRecords(cwslg_fetch_ft4_sync, out, max, nullptr); }
     // FT8 channels with Context::enableFt8Softbits: record q (174 bit metrics, sigma, nsync) belongs to entry q of candidates() of the same
     // epoch -- cwslg_fetch_ft8_softbits; 0 records while none of the current epoch exist
     int fetchFt8Softbits(std::vector<cwslg_ft8_soft> &out, int max = 600, std::uint64_t *startEpoch = nullptr)
-    {
-        out.resize(max);
-        int n = 0;
-        const int rc = cwslg_fetch_ft8_softbits(ctx_.raw(), id_, out.data(), max, &n, startEpoch);
-        if (rc == CWSLG_ERR_NO_FRAME) { out.clear(); return 0; }
-        check(ctx_.raw(), rc);
-        out.resize(n);
-        return n;
-    }
+    { return fetchRecords(cwslg_fetch_ft8_softbits, out, max, startEpoch); }
     // FT8 channels with Context::enableFt8Decode: record q (91 bits, iters, nbad, nharderr, crc_ok) belongs to entry q of candidates() of the same
     // epoch -- cwslg_fetch_ft8_decode; 0 records while none of the current epoch exist
     int fetchFt8Decode(std::vector<cwslg_ft8_msg> &out, int max = 600, std::uint64_t *startEpoch = nullptr)
-    {
-        out.resize(max);
-        int n = 0;
-        const int rc = cwslg_fetch_ft8_decode(ctx_.raw(), id_, out.data(), max, &n, startEpoch);
-        if (rc == CWSLG_ERR_NO_FRAME) { out.clear(); return 0; }
-        check(ctx_.raw(), rc);
-        out.resize(n);
-        return n;
-    }
+    { return fetchRecords(cwslg_fetch_ft8_decode, out, max, startEpoch); }
     // FT4 channels with Context::enableFt4Decode: record q (three cwslg_ft8_msg, one per metric set) belongs to entry q of cwslg_fetch_ft4_sync of
     // the same epoch -- cwslg_fetch_ft4_decode; 0 records while none of the current epoch exist
     int fetchFt4Decode(std::vector<cwslg_ft4_msg> &out, int max = 1800, std::uint64_t *startEpoch = nullptr)
-    {
-        out.resize(max);
-        int n = 0;
-        const int rc = cwslg_fetch_ft4_decode(ctx_.raw(), id_, out.data(), max, &n, startEpoch);
-        if (rc == CWSLG_ERR_NO_FRAME) { out.clear(); return 0; }
-        check(ctx_.raw(), rc);
-        out.resize(n);
-        return n;
-    }
+    { return fetchRecords(cwslg_fetch_ft4_decode, out, max, startEpoch); }
     // FT4 channels with Context::enableFt4Osd: record q (three cwslg_osd_msg, one per metric set) belongs to entry q of cwslg_fetch_ft4_sync of
     // the same epoch -- cwslg_fetch_ft4_osd; 0 records while none of the current epoch exist
     int fetchFt4Osd(std::vector<cwslg_ft4_osd> &out, int max = 1800, std::uint64_t *startEpoch = nullptr)
-    {
-        out.resize(max);
-        int n = 0;
-        const int rc = cwslg_fetch_ft4_osd(ctx_.raw(), id_, out.data(), max, &n, startEpoch);
-        if (rc == CWSLG_ERR_NO_FRAME) { out.clear(); return 0; }
-        check(ctx_.raw(), rc);
-        out.resize(n);
-        return n;
-    }
+    { return fetchRecords(cwslg_fetch_ft4_osd, out, max, startEpoch); }
     // FT8 channels with Context::enableFt8Osd: record q (91 bits, dmin, nharderr, nskip, crc_ok, how, flip) belongs to entry q of candidates() of
     // the same epoch -- cwslg_fetch_ft8_osd; 0 records while none of the current epoch exist
     int fetchFt8Osd(std::vector<cwslg_osd_msg> &out, int max = 600, std::uint64_t *startEpoch = nullptr)
-    {
-        out.resize(max);
-        int n = 0;
-        const int rc = cwslg_fetch_ft8_osd(ctx_.raw(), id_, out.data(), max, &n, startEpoch);
-        if (rc == CWSLG_ERR_NO_FRAME) { out.clear(); return 0; }
-        check(ctx_.raw(), rc);
-        out.resize(n);
-        return n;
-    }
+    { return fetchRecords(cwslg_fetch_ft8_osd, out, max, startEpoch); }
     // FT4 channels with Context::enableFt4Softbits: record q (three sets of 174 bit metrics, their sigma, nsync, nqual) belongs to entry q of
     // cwslg_fetch_ft4_sync of the same epoch -- cwslg_fetch_ft4_softbits; 0 records while none of the current epoch exist
     int fetchFt4Softbits(std::vector<cwslg_ft4_soft> &out, int max = 1800, std::uint64_t *startEpoch = nullptr)
-    {
-        out.resize(max);
-        int n = 0;
-        const int rc = cwslg_fetch_ft4_softbits(ctx_.raw(), id_, out.data(), max, &n, startEpoch);
-        if (rc == CWSLG_ERR_NO_FRAME) { out.clear(); return 0; }
-        check(ctx_.raw(), rc);
-        out.resize(n);
-        return n;
-    }
+    { return fetchRecords(cwslg_fetch_ft4_softbits, out, max, startEpoch); }
     // what decodeUsingShMem does between lock and unlock (DecoderPool.hpp:451-590): the jt9 block, d2 straight from HBM
     bool fillDecoderBlock(void *block, std::size_t bytes, int decodedepth, int highestDecodeFreq, std::uint64_t &startEpoch, bool js8 = false)
     {
@@ -312,6 +256,17 @@ public:
         return true;
     }
 private:
+    // one record fetch of the C ABI into `out`, sized to what came back: the number of records, 0 (and `out` empty) while there are none to fetch
+    template <class Rec, class Fetch> int fetchRecords(Fetch fetch, std::vector<Rec> &out, int max, std::uint64_t *startEpoch)
+    {
+        out.resize(max);
+        int n = 0;
+        const int rc = fetch(ctx_.raw(), id_, out.data(), max, &n, startEpoch);
+        if (rc == CWSLG_ERR_NO_FRAME) { out.clear(); return 0; }
+        check(ctx_.raw(), rc);
+        out.resize(n);
+        return n;
+    }
     Context &ctx_;
     int id_ = -1;
     std::string mode_;

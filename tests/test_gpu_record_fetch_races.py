@@ -1,6 +1,6 @@
 """GPU: the record fetches of the decode chain raced against the next boundary (ABI 5: "results are handed out whole, per epoch").  The seven
 fetches behind the candidate lists -- cwslg_fetch_ft8_softbits / _decode / _osd and cwslg_fetch_ft4_sync / _softbits / _decode / _osd -- each
-carry their own copy of the ticket, event and epoch logic and their own stamp; the arithmetic of every stage is pinned elsewhere.  Here a slot
+have a stamp of their own and share the ticket, event and epoch logic (csrc/record_kinds.hpp, sync_host.inc); the arithmetic of every stage is pinned elsewhere.  Here a slot
 clock runs free while consumers fetch, and ONE rule is applied to whatever comes back: records returned with start epoch e are, byte for byte
 (the count included), tests/record_race_cases.py:expected() of that channel, that epoch and the configuration in force at that epoch's
 boundary -- and a stage that did not run at e hands out nothing stamped e.  A fetch may come back empty-handed (CWSLG_ERR_NO_FRAME); where that

@@ -142,7 +142,7 @@ def test_ft4_many_channels_one_boundary(ctx, oracle):
 def test_both_features_ft8_and_ft4_together(xctx, oracle):
     """Gap 2, both features on in one context: 5 FT8 and 3 FT4 channels on one receiver, cwslg_enable_ft8_softbits and cwslg_enable_ft4_softbits
     both on, so that sync_ensure_channel decides the FT8 channels' allocation from cfg.ft8_soft (row pitch cfg.nbins, d_soft behind the list) while
-    the FT4 channels keep FT4_ROW and get their record arrays from ft4s_ensure_channel.
+    the FT4 channels keep FT4_ROW and get their record arrays from ensure_record_array.
 
     One boundary CANNOT carry both groups: cwslg_slot_boundary and cwslg_slot_boundary_begin collect `c->chans[k].group == group` only, FT8 and FT4
     are groups 0 and 1 (cwslg_slot_boundary_channel takes one channel), and boundary_locked calls sync_launch with the ids it was given.  n8 > 0 with
@@ -211,14 +211,14 @@ def test_reconfigure_between_slots_with_soft_bits_on(xctx, oracle):
     before each slot cwslg_enable_sync is called again -- max_cand 100 -> 7 -> 200, then f_hi 3000 -> 2959 -> 3100 (FT8 pitch 992 -> 992 -> 1024,
     checked against ft8_softbits_ref.soft_pitch), candidate order "freq" for the fifth slot and "sync" again for the sixth -- so that
     sync_ensure_channel frees and reallocates everything (`b.max_cand == cfg.max_cand`, `b.nbins == want_bins` fail), d_soft included, and
-    ft4s_ensure_channel sizes its array again from b.max_cand.
+    ensure_record_array's caller sizes the FT4 array again from b.max_cand.
 
-    Contract of a re-enable, from sync_host.inc, cwslg_enable_sync: `cfg.ft8_soft = c->sync_cfg.ft8_soft;` / `cfg.ft4_soft = c->sync_cfg.ft4_soft;`
-    and `if (cfg.ft8_soft) cfg.nbins = (cfg.ib + 15 + 31) / 32 * 32;` -- the features stay on and the pitch is recomputed; asserted here by the
+    Contract of a re-enable, from sync_host.inc, cwslg_enable_sync: `cfg.kept = c->sync_cfg.kept;` (SyncConfig::Kept holds ft8_soft and ft4_soft)
+    and `if (cfg.kept.ft8_soft) cfg.nbins = (cfg.ib + 15 + 31) / 32 * 32;` -- the features stay on and the pitch is recomputed; asserted here by the
     records being there after the next boundary without another enable call.
     Between the re-enable and the next boundary the previous slot's records are HANDED OUT UNCHANGED: nothing is reallocated before the boundary
     (sync_launch -> sync_ensure_channel), the epochs still agree, and the fetches size themselves by the channel's own buffers
-    (cwslg_fetch_ft8_softbits: `lim = std::min(std::max(max, 0), ch.syncbuf.max_cand);`, cwslg_fetch_ft4_softbits: `lim = ch.syncbuf.max_cand;`),
+    (fetch_begin: `ch.syncbuf.max_cand` is the source's `cap`; fetch_flat: `lim = std::min(std::max(max, 0), s.cap);`, fetch_walk: `std::min(cnt, s.cap)`),
     not by the new configuration -- so the count cannot shrink to the new max_cand nor the contents change.
 
     After every slot: list, FT4 records and both kinds of soft records exact, record counts inside the current max_cand, each fetch under the
@@ -404,8 +404,9 @@ def test_ft4_refine_and_soft_bits_at_the_band_edges(ctx, oracle):
 
 def test_fetch_slot_agrees_with_the_soft_fetches(xctx, oracle):
     """Gap 6, cwslg_fetch_slot next to the soft-bit fetches: one FT8 and one FT4 channel, both features on.  The one-ticket fetch
-    (cwsl_gpu.hip, cwslg_fetch_slot: `out->start_epoch = ch.frame_t0;`, the list only `if (ch.cand_t0 == ch.frame_t0 && ch.cand_t0 != 0)`) and the
-    separate fetches (cwslg_fetch_ft8_softbits / cwslg_fetch_ft4_softbits: records only while soft_t0 / soft4_t0 == cand_t0 == frame_t0) agree on
+    (cwsl_gpu.hip, cwslg_fetch_slot: `out->start_epoch = ch.frame_t0;`, the list only `if (... && channel_records_epoch(ch, REC_CAND, ch.syncbuf.d_block, true))`:
+    its stamp is the frame's epoch and not 0) and the separate fetches (cwslg_fetch_ft8_softbits / cwslg_fetch_ft4_softbits: records only while the
+    REC_SOFT8 / REC_SOFT4 rule of csrc/record_kinds.hpp holds, own stamp == the list's == frame_t0) agree on
     epoch, list and record order: t_start, list and ft4_sync are equal, and soft record k belongs to list entry / sync record k of THAT ticket --
     three records of each kind are recomputed with the restatement from fetch_slot's own frame and list."""
     ctx = xctx
