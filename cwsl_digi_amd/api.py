@@ -148,6 +148,12 @@ def ft4_best_word(msg, osd):
     return (int(best), bool(by_osd)) if best.ndim == 0 else (best.astype(np.int64), by_osd)
 
 
+# numpy view of cwslg_decode (40 bytes): one de-duplicated decoded word of a channel, as cwslg_fetch_decodes hands them out
+DECODE_DTYPE = np.dtype([("ch_id", np.int32), ("entry", np.int16), ("by_osd", np.uint8), ("set", np.uint8), ("bits", np.uint8, 12), ("freq_hz", np.float32),
+                         ("dt_s", np.float32), ("sync", np.float32), ("dmin", np.float32), ("nharderr", np.int16), ("ndup", np.uint16)])
+assert DECODE_DTYPE.itemsize == 40
+
+
 class Ft4Soft(C.Structure):
     _fields_ = [("llr", (C.c_float * 174) * 3), ("sigma", C.c_float * 3), ("nsync", C.c_int32), ("nqual", C.c_int32), ("pad_", C.c_int32)]
 
@@ -195,7 +201,7 @@ ABI_SYMBOLS = [
     "cwslg_enable_ft8_softbits", "cwslg_fetch_ft8_softbits", "cwslg_enable_ft4_softbits", "cwslg_fetch_ft4_softbits", "cwslg_sync_debug_fetch", "cwslg_get_stats", "cwslg_reset_stats",
     "cwslg_set_ldpc_code", "cwslg_enable_ft8_decode", "cwslg_fetch_ft8_decode", "cwslg_ldpc_decode",
     "cwslg_enable_ft8_osd", "cwslg_fetch_ft8_osd", "cwslg_osd_decode", "cwslg_enable_ft4_decode", "cwslg_fetch_ft4_decode",
-    "cwslg_enable_ft4_osd", "cwslg_fetch_ft4_osd",
+    "cwslg_enable_ft4_osd", "cwslg_fetch_ft4_osd", "cwslg_fetch_decodes",
     "cwslg_set_timing", "cwslg_demod_kernel_name", "cwslg_stream", "cwslg_channel_constants", "cwslg_phasor_checkpoint_stride", "cwslg_channel_phasor_checkpoints",
     "cwslg_slot_clock_next", "cwslg_pool_sizing", "cwslg_find_band", "cwslg_parse_decode_line",
     "cwslg_decoder_block_bytes", "cwslg_decoder_block_field", "cwslg_fill_decoder_block", "cwslg_decoder_route", "cwslg_decoder_command",
@@ -296,6 +302,7 @@ def load_library(build_if_missing=True):
     L.cwslg_fetch_ft4_decode.argtypes = [vp, i32, C.POINTER(Ft4Msg), i32, C.POINTER(i32), C.POINTER(u64)]
     L.cwslg_enable_ft4_osd.argtypes = [vp, i32, i32, i32, i32]
     L.cwslg_fetch_ft4_osd.argtypes = [vp, i32, C.POINTER(Ft4Osd), i32, C.POINTER(i32), C.POINTER(u64)]
+    L.cwslg_fetch_decodes.argtypes = [vp, i32, C.POINTER(u64), vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     L.cwslg_sync_debug_fetch.argtypes = [vp, i32, i32, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(i32)]
     L.cwslg_get_stats.argtypes = [vp, C.POINTER(Stats)]
     L.cwslg_reset_stats.argtypes = [vp]
@@ -796,6 +803,20 @@ class Context:
         n, t0 = r
         rec = buf[:n].copy()
         return (rec, t0) if with_epoch else rec
+
+    def fetch_decodes(self, group, start_epoch=0, max=4096):
+        """cwslg_fetch_decodes: the decoded words of a whole FT8 / FT4 slot-clock group ("FT8" / "FT4" or a group number) in one fetch, chosen
+        (BP before OSD) and de-duplicated per channel on the device.  start_epoch 0: the newest epoch any channel of the group has decode records
+        of.  -> None if no channel takes part (CWSLG_ERR_NO_FRAME), else (records, start_epoch, n_total, n_channels): records a numpy array
+        (DECODE_DTYPE) of the first min(n_total, max) decodes in ascending (ch_id, entry)."""
+        g = (GROUPS[group] if group in GROUPS else _MODE_GROUP[group]) if isinstance(group, str) else int(group)
+        buf = np.zeros(int(max) if int(max) > 1 else 1, DECODE_DTYPE)
+        t0, n, n_total, n_ch = C.c_uint64(int(start_epoch)), C.c_int(), C.c_int(), C.c_int()
+        rc = self.L.cwslg_fetch_decodes(self.h, g, C.byref(t0), buf.ctypes.data if int(max) > 0 else None, int(max), C.byref(n), C.byref(n_total), C.byref(n_ch))
+        if rc == ERR_NO_FRAME:
+            return None
+        self._chk(rc)
+        return buf[:n.value].copy(), t0.value, n_total.value, n_ch.value
 
     def enable_long_sync(self, on=True, nfa_hz=1400, nfb_hz=1600, minsync=1.2):
         """Candidate search of the 120 s modes (WSPR: wsprd's front end; FST4W-120: get_candidates_fst4 over nfa..nfb)."""

@@ -52,6 +52,7 @@
 #include "osd_kernels.hpp"
 #include "ft4soft_kernels.hpp"
 #include "longsync_kernels.hpp"
+#include "harvest_kernels.hpp"
 
 namespace cwslg {
 
@@ -217,6 +218,15 @@ struct WorkBuf {
     bool in_flight = false;
 };
 
+// cwslg_fetch_decodes (harvest_kernels.hpp): the staging of one slot-clock group -- a pinned block (descriptors up, n_total + records down) and a
+// device block (descriptors, counts, offsets, n_total + records), allocated by the group's first call, grown on demand, freed by cwslg_destroy.
+// `mu` serialises the calls of the group (order: this mutex, then the context's).
+struct HarvestStage {
+    std::mutex mu;
+    char *h = nullptr, *d = nullptr;
+    size_t h_bytes = 0, d_bytes = 0;
+};
+
 struct TimedSpan {
     hipEvent_t a, b;
     int kind;                          // 0 demod, 1 finalize, 2 sync stage (whole), 3 / 4 its FT8 spectra / search + selection kernels
@@ -309,6 +319,7 @@ struct cwslg_ctx {
     bool ft4_dft_valu = false;         // CWSLG_FT4_DFT=valu
     LongConfig long_cfg;
     LongShared long_shared;
+    HarvestStage harvest[2];           // cwslg_fetch_decodes: [0] the FT8 group's, [1] the FT4 group's
     // side stream: optionally (CWSLG_SYNC_VARIANT bit 3) carries the FT8 candidate kernel next to the following demod launch
     hipStream_t side = nullptr;
     hipEvent_t sync2d_done = nullptr, cand_done = nullptr, sync_tail = nullptr;
@@ -1250,6 +1261,10 @@ void cwslg_destroy(cwslg_ctx *c)
     sync_free_shared(c->sync_shared);
     long_free_shared(c->long_shared);
     if (c->d_sincos) hipFree(c->d_sincos);
+    for (HarvestStage &hs : c->harvest) {
+        if (hs.h) (void)hipHostFree(hs.h);
+        if (hs.d) (void)hipFree(hs.d);
+    }
     if (c->clk_h) (void)hipHostFree(c->clk_h);
     for (hipStream_t fs : c->fetch_stream) if (fs) { (void)hipStreamSynchronize(fs); (void)hipStreamDestroy(fs); }
     for (hipEvent_t e : c->fetch_ev) if (e) (void)hipEventDestroy(e);

@@ -212,7 +212,7 @@ int long_sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
 #endif
         hipLaunchKernelGGL((fftb_stage1_kernel<45, 1024>), dim3(1024 / 64, 1, n), dim3(FFTB_S1_NT), 0, c->stream, d, tb, tb.wfull, 1, 1);
         hipLaunchKernelGGL((fftb_stage2_kernel<45, 1024>), dim3((45 + 3) / 4, 1, n), dim3(256), 0, c->stream, d, tb, 1);
-        hipLaunchKernelGGL(wspr_iq_kernel, dim3((WSPR_IQ_LEN + 255) / 256, n), dim3(256), 0, c->stream, d);
+        hipLaunchKernelGGL(long_pack_kernel, dim3((WSPR_IQ_LEN + 255) / 256, n), dim3(256), 0, c->stream, d, LONG_PACK_WSPR_IQ);
         hipLaunchKernelGGL(wspr_spectra_kernel, dim3(WSPR_NFFTS, n), dim3(256), 0, c->stream, d, (const float2 *)s.d_w512, (const float *)s.d_win512);
         hipLaunchKernelGGL(wspr_peaks_kernel, dim3(n), dim3(512), 0, c->stream, d);
         hipLaunchKernelGGL(wspr_coarse_kernel, dim3(WSPR_MAXCAND, n), dim3(256), 0, c->stream, d, (const unsigned char *)s.d_pr3);

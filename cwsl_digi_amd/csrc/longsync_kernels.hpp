@@ -406,8 +406,9 @@ __global__ __launch_bounds__(256) void wspr_combine_kernel(const LongWork *__res
     }
 }
 
-// idat/qdat = conj(inverse output) / 1000 (double division, as `fftout/1000.0`), zero tail.  grid (IQ_LEN / 256, channels)
-__global__ __launch_bounds__(256) void wspr_iq_kernel(const LongWork *__restrict__ works)
+// idat/qdat = conj(inverse output) / 1000 (double division, as `fftout/1000.0`), zero tail.  grid (IQ_LEN / 256, channels); the third body of
+// long_pack_kernel below (selector 2)
+__device__ __forceinline__ void wspr_iq(const LongWork *__restrict__ works)
 {
     const LongWork *w = works + blockIdx.y;
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -637,13 +638,16 @@ __device__ __forceinline__ void fst4w_pack(const LongWork *__restrict__ works, f
     }
 }
 
-// The two pack passes as ONE kernel (the product library's inventory is capped): `fst4w` selects the body, wave-uniformly; each body is the
-// instruction stream it was as a kernel of its own and takes the LDS it took (dynamic: LONG_PACK_LDS_WSPR / _FST4W bytes at the launch).
+// The two pack passes and WSPR's idat/qdat pass as ONE kernel (the product library's inventory is capped): `fst4w` selects the body, wave-uniformly
+// -- 0 wspr_pack, 1 fst4w_pack, 2 wspr_iq; each body is the instruction stream it was as a kernel of its own and takes the LDS it took (dynamic:
+// LONG_PACK_LDS_WSPR / _FST4W bytes at the launch, none for wspr_iq).
 constexpr unsigned LONG_PACK_LDS_WSPR = (WSPR_R * 256 + 256) * sizeof(float), LONG_PACK_LDS_FST4W = F4W_R * 256 * sizeof(float);
+constexpr int LONG_PACK_WSPR = 0, LONG_PACK_FST4W = 1, LONG_PACK_WSPR_IQ = 2;
 __global__ __launch_bounds__(256) void long_pack_kernel(const LongWork *__restrict__ works, int fst4w)
 {
     extern __shared__ float s_pack[];
-    if (fst4w) fst4w_pack(works, s_pack);
+    if (fst4w == LONG_PACK_WSPR_IQ) wspr_iq(works);
+    else if (fst4w) fst4w_pack(works, s_pack);
     else wspr_pack(works, s_pack);
 }
 

@@ -957,6 +957,99 @@ int cwslg_fetch_ft4_osd(cwslg_ctx *c, int ch_id, cwslg_ft4_osd *dst, int max, in
     return fetch_walk(c, ch_id, REC_OSD4, dst, sizeof(cwslg_ft4_osd), max, n, start_epoch);
 }
 
+// The decoded words of a whole FT8 / FT4 group (harvest_kernels.hpp; the contract is the header's).  A fetch like the others -- pointers read
+// under the context mutex, one ticket of the group, the work on a fetch stream behind the group's generation event with the mutex released --
+// except that what runs on the fetch stream is a descriptor upload, decode_harvest_kernel (count, scan, emit) and ONE copy down.  It writes only
+// the group's HarvestStage: no record, list, stamp or statistic changes.
+int cwslg_fetch_decodes(cwslg_ctx *c, int group, uint64_t *start_epoch, cwslg_decode *dst, int max, int *n, int *n_total, int *n_channels)
+{
+    static_assert(sizeof(cwslg_decode) == HARVEST_REC_WORDS * sizeof(unsigned), "record layout");
+    if (n) *n = 0;
+    if (n_total) *n_total = 0;
+    if (n_channels) *n_channels = 0;
+    if (!c || !start_epoch || !n || !n_total || (max > 0 && !dst)) return CWSLG_ERR_ARG;
+    if (group != CWSLG_GROUP_FT8 && group != CWSLG_GROUP_FT4) return fail(c, CWSLG_ERR_ARG, "decodes exist for the FT8 and FT4 groups only (group %d)", group);
+    const bool ft4 = group == CWSLG_GROUP_FT4;
+    const int k_msg = ft4 ? REC_MSG4 : REC_MSG8, k_osd = ft4 ? REC_OSD4 : REC_OSD8;
+    HarvestStage &hs = c->harvest[ft4 ? 1 : 0];
+    std::lock_guard<std::mutex> serial(hs.mu);
+    std::vector<HarvestDesc> descs;
+    size_t bound = 0;                   // no more decodes than entries
+    ResultFetch rf;                     // ticket + lifetime, released when the copy is done or the call fails
+    {
+        std::lock_guard<std::mutex> g(c->mu);
+        uint64_t E = *start_epoch;
+        std::vector<std::pair<int, uint64_t>> live;
+        for (size_t id = 0; id < c->chans.size(); ++id) {
+            const Channel &ch = c->chans[id];
+            if (!ch.open || ch.group != group || !(ft4 ? ch.sync_ft4 : ch.sync_ft8)) continue;      // (a JS8 channel of the FT8 group has no chain)
+            const uint64_t e = channel_records_epoch(ch, k_msg, ch.syncbuf.d_block);
+            if (e) live.emplace_back((int)id, e);
+        }
+        if (!E) for (const auto &l : live) E = std::max(E, l.second);
+        for (const auto &l : live) {
+            if (l.second != E) continue;
+            const Channel &ch = c->chans[l.first];
+            const SyncChannelBuffers &b = ch.syncbuf;
+            const bool osd = channel_records_epoch(ch, k_osd, b.d_block) == E;
+            HarvestDesc d{};
+            d.cnt = b.d_ncand;
+            d.list = ft4 ? b.d_rec : (const void *)b.d_cand;
+            d.nrec = ft4 ? b.d_nrec : nullptr;
+            d.msg = record_array(b, k_msg);
+            d.osd = osd ? record_array(b, k_osd) : nullptr;
+            d.cap = std::min(b.max_cand, (int)SYNC_MAXCAND_CAP);
+            d.ch_id = l.first;
+            descs.push_back(d);
+            bound += (size_t)d.cap * (ft4 ? 3 : 1);
+        }
+        if (descs.empty()) return CWSLG_ERR_NO_FRAME;
+        *start_epoch = E;
+        hipSetDevice(c->device);
+        const int rc = begin_result_fetch(c, c->chans[descs[0].ch_id], rf);
+        if (rc) return rc;
+    }
+    // no context lock from here on
+    const size_t nch = descs.size(), lim = std::min((size_t)std::max(max, 0), bound);
+    auto pad = [](size_t v) { return (v + 255) & ~size_t(255); };
+    const size_t desc_bytes = nch * sizeof(HarvestDesc), cnt_bytes = pad(nch * sizeof(unsigned));
+    const size_t out_bytes = (HARVEST_HEAD_WORDS + lim * HARVEST_REC_WORDS) * sizeof(unsigned);
+    const size_t h_need = pad(desc_bytes) + out_bytes, d_need = pad(desc_bytes) + 2 * cnt_bytes + out_bytes;
+    if (hs.h_bytes < h_need) {
+        if (hs.h) (void)hipHostFree(hs.h);
+        hs.h = nullptr; hs.h_bytes = 0;
+        HIPCHK(c, hipHostMalloc((void **)&hs.h, pad(h_need + h_need / 2), hipHostMallocDefault));
+        hs.h_bytes = pad(h_need + h_need / 2);
+    }
+    if (hs.d_bytes < d_need) {
+        if (hs.d) (void)hipFree(hs.d);
+        hs.d = nullptr; hs.d_bytes = 0;
+        HIPCHK(c, hipMalloc((void **)&hs.d, pad(d_need + d_need / 2)));
+        hs.d_bytes = pad(d_need + d_need / 2);
+    }
+    std::memcpy(hs.h, descs.data(), desc_bytes);
+    unsigned *h_out = (unsigned *)(hs.h + pad(desc_bytes));
+    const HarvestDesc *d_desc = (const HarvestDesc *)hs.d;
+    unsigned *d_counts = (unsigned *)(hs.d + pad(desc_bytes)), *d_offsets = (unsigned *)(hs.d + pad(desc_bytes) + cnt_bytes);
+    unsigned *d_out = (unsigned *)(hs.d + pad(desc_bytes) + 2 * cnt_bytes);
+    HIPCHK(c, hipStreamWaitEvent(rf.fs, rf.ev, 0));
+    HIPCHK(c, hipMemcpyAsync(hs.d, hs.h, desc_bytes, hipMemcpyHostToDevice, rf.fs));
+    for (int mode : {HARVEST_COUNT, HARVEST_SCAN, HARVEST_EMIT}) {
+        if (mode == HARVEST_EMIT && lim == 0) break;               // nothing may be written: the total is all the caller gets
+        hipLaunchKernelGGL(decode_harvest_kernel, dim3(mode == HARVEST_SCAN ? 1u : (unsigned)nch), dim3(HARVEST_NT), 0, rf.fs, d_desc, d_counts, d_offsets, d_out,
+                           (int)nch, (int)lim, ft4 ? 1 : 0, mode);
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(h_out, d_out, out_bytes, hipMemcpyDeviceToHost, rf.fs));
+    HIPCHK(c, hipStreamSynchronize(rf.fs));
+    const size_t total = h_out[0], got = std::min(total, lim);
+    if (got) std::memcpy(dst, h_out + HARVEST_HEAD_WORDS, got * sizeof(cwslg_decode));
+    *n = (int)got;
+    *n_total = (int)total;
+    if (n_channels) *n_channels = (int)nch;
+    return CWSLG_OK;
+}
+
 int cwslg_sync_debug_fetch(cwslg_ctx *c, int ch_id, int what, void *dst, size_t cap_bytes, size_t *n_items, int *row_len)
 {
     if (!c || !dst) return CWSLG_ERR_ARG;

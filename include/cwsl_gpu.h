@@ -423,8 +423,8 @@ int cwslg_fetch_ft8_softbits(cwslg_ctx *ctx, int ch_id, cwslg_ft8_soft *dst, int
 /* FT8 decode (row a13; PARITY UNPINNED): flooding sum-product decoding of the LDPC(174,91) code on the 174 metrics of every cwslg_ft8_soft record,
  * then the CRC-14 -- the first consumer of those metrics, on the device: per candidate 91 bits, "is a codeword", "CRC matches" and an iteration
  * count (20 bytes) instead of 704 bytes over the link and belief propagation on the host.  Structured like upstream bpdecode174_91.  Out of scope:
- * ordered-statistics decoding (a stage of its own: FT8 OSD below), a-priori passes, signal subtraction, unpacking the 77 bits into text, de-duplication (neighbouring candidates of
- * one transmission repeat one message).  Off by default; while it is off nothing changes (launches, buffers, upload bytes, lists, records).
+ * ordered-statistics decoding (a stage of its own: FT8 OSD below), a-priori passes, signal subtraction, unpacking the 77 bits into text.  De-duplication (neighbouring candidates of
+ * one transmission repeat one message) is not this stage's either: cwslg_fetch_decodes below hands the words of a whole group out chosen and de-duplicated.  Off by default; while it is off nothing changes (launches, buffers, upload bytes, lists, records).
  *   The code is DATA THE CALLER LOADS: the WSJT-X source is not part of this repository and its parity-check table is not reproduced here.
  *       cwslg_set_ldpc_code takes the 83 x 7 table `Nm` of the integrator's own WSJT-X tree (recalled, not checked here, as lib/ft8/ldpc_174_91_c_parity.f90), row-major: entry =
  *       1-based codeword position 1..174, a row of weight 6 ends in one 0.  Validation: every position 1..174 occurs exactly three times; row
@@ -615,6 +615,47 @@ int cwslg_fetch_ft4_decode(cwslg_ctx *ctx, int ch_id, cwslg_ft4_msg *dst, int ma
 typedef struct { cwslg_osd_msg set[3]; } cwslg_ft4_osd;          /* 72 bytes */
 int cwslg_enable_ft4_osd(cwslg_ctx *ctx, int enable, int order, int min_nsync, int min_nqual);
 int cwslg_fetch_ft4_osd(cwslg_ctx *ctx, int ch_id, cwslg_ft4_osd *dst, int max, int *n, uint64_t *start_epoch);
+/* The decodes of a slot: the words of a whole FT8 or FT4 slot-clock group in ONE fetch, chosen (BP before OSD; FT4: the set ft4BestWord takes)
+ * and de-duplicated per channel on the device.  Without it a consumer calls cwslg_fetch_candidates, cwslg_fetch_ft8_decode and cwslg_fetch_ft8_osd
+ * for every channel (three tickets and stream synchronisations each), copies 64 bytes per list entry although a handful of entries per channel
+ * carry a word, and picks and de-duplicates on the host.  A FETCH, not a stage: no record kind, no stamp, no launch at a boundary; the kernel
+ * (decode_harvest_kernel: count, scan, emit) runs inside the call, on the fetch stream.
+ *   1. group is CWSLG_GROUP_FT8 or CWSLG_GROUP_FT4, anything else CWSLG_ERR_ARG; so is a null ctx, start_epoch, n or n_total, or dst null with
+ *      max > 0.  n_channels may be null.
+ *   2. A channel takes part only if it is open, belongs to the group, has that chain's sync stage (an FT8 / FT4 channel: a JS8 channel of the FT8
+ *      group does not take part) and the rule that governs cwslg_fetch_ft8_decode / cwslg_fetch_ft4_decode gives it an epoch E_ch != 0 -- decode
+ *      records, soft records, list and frame of one epoch.  The slot epoch is E = *start_epoch; *start_epoch == 0 means the largest E_ch among such
+ *      channels.  The channels that take part are those with E_ch == E.  None: CWSLG_ERR_NO_FRAME, all counts 0, *start_epoch untouched.
+ *      Otherwise *start_epoch = E.
+ *   3. A taking-part channel's OSD records are used only if the rule of cwslg_fetch_ft8_osd / cwslg_fetch_ft4_osd also gives them epoch E.
+ *   4. The entries are all min(count, max_cand) entries of the list; FT4: the sync records in the order cwslg_fetch_ft4_sync compacts them.
+ *      The word of an entry -- FT8: the decode record's if its crc_ok is set; otherwise, if OSD is used and the OSD record's crc_ok is set, the OSD
+ *      record's.  FT4: the smallest set with BP crc_ok; failing that, if OSD is used, the smallest set with OSD crc_ok.  An entry without a word
+ *      contributes nothing, and neither does a word whose 91 bits are all zero (its CRC is 0, so it would otherwise pass).
+ *   5. Per channel, entries with equal bits[12] are ONE decode: the entry reported is the smallest by (by_osd, nharderr, entry); ndup counts all
+ *      entries that carried the word.  Words are never compared across channels.
+ *   6. Order: ascending ch_id, then ascending entry.  *n_total counts every decode; *n = min(*n_total, max) and the first *n are written;
+ *      *n_channels = channels that took part.  Two calls on the same epoch return the same bytes.
+ *   7. The call takes one ticket of the group and runs on a fetch stream behind the group's generation event, like every fetch: the group's next
+ *      boundary waits for it.  Concurrent calls on one group are serialised by the library.  It is not counted in stats.sync_launches, adds no
+ *      field to cwslg_stats, and never changes records, lists or stamps.  Its device and pinned staging blocks are allocated at the group's first
+ *      call (a context that never calls it holds no byte of them) and freed by cwslg_destroy.
+ * Out of scope: rvec descrambling, unpacking the 77 bits into text, comparing words across channels or slots. */
+typedef struct {
+    int32_t  ch_id;
+    int16_t  entry;      /* FT8: index into the candidate list; FT4: index of the sync record as cwslg_fetch_ft4_sync compacts them */
+    uint8_t  by_osd;     /* 0: word of the decode record (BP); 1: word of the OSD record */
+    uint8_t  set;        /* FT4: metric set 0..2 the word came from; FT8: 0 */
+    uint8_t  bits[12];   /* as cwslg_ft8_msg.bits */
+    float    freq_hz;    /* FT8: candidate freq_hz; FT4: record f1_hz */
+    float    dt_s;       /* FT8: candidate dt_s; FT4: record dt_s */
+    float    sync;       /* FT8: candidate sync; FT4: record sync */
+    float    dmin;       /* by_osd: the OSD record's dmin; else +0 */
+    int16_t  nharderr;   /* of the record the word came from */
+    uint16_t ndup;       /* entries of this channel that carried this word, this one included; saturates at 65535 */
+} cwslg_decode;          /* 40 bytes */
+int cwslg_fetch_decodes(cwslg_ctx *ctx, int group, uint64_t *start_epoch /* in/out */, cwslg_decode *dst, int max, int *n, int *n_total,
+                        int *n_channels);
 int cwslg_fetch_slot(cwslg_ctx *ctx, int ch_id, int16_t *frame, size_t cap, void *list, size_t list_bytes,
                      cwslg_ft4_sync *ft4, int max_ft4, cwslg_slot_result *out);
 int cwslg_set_ft4_syncmin(cwslg_ctx *ctx, float syncmin);

@@ -113,6 +113,20 @@ public:
         out.resize(n);
         check(c_, cwslg_osd_decode(c_, llr, n, order, out.data()));
     }
+    // The decodes of a slot: the words of a whole FT8 / FT4 slot-clock group in one fetch, chosen (BP before OSD) and de-duplicated per channel on
+    // the device (cwslg_fetch_decodes).  startEpoch in / out: 0 asks for the newest epoch any channel of the group has decode records of.  `out`
+    // gets the first min(total, max) decodes in ascending (ch_id, entry); the return value is the total; 0 with `out` empty and startEpoch
+    // untouched while no channel takes part.  nChannels (optional): channels that took part.
+    int fetchDecodes(int group, std::vector<cwslg_decode> &out, std::uint64_t &startEpoch, int max = 4096, int *nChannels = nullptr)
+    {
+        out.resize(max > 0 ? max : 0);
+        int n = 0, total = 0;
+        const int rc = cwslg_fetch_decodes(c_, group, &startEpoch, out.data(), static_cast<int>(out.size()), &n, &total, nChannels);
+        if (rc == CWSLG_ERR_NO_FRAME) { out.clear(); return 0; }
+        check(c_, rc);
+        out.resize(n);
+        return total;
+    }
     void synchronize() { check(c_, cwslg_synchronize(c_)); }
     // One block for each of several receivers in ONE call (cwslg_push_iq_many): for a host that serves thousands of streams, where a
     // per-receiver push per block (Receiver.hpp:242-249, ReceiverPort::push below) would mean hundreds of thousands of copies a second.
