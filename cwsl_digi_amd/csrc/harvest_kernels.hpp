@@ -201,4 +201,16 @@ __global__ __launch_bounds__(HARVEST_NT) void decode_harvest_kernel(const Harves
     if (mode == HARVEST_COUNT && tid == 0) g_counts[ch] = n_out;
 }
 
+// The launches of one call on stream `s`: count and emit with one workgroup per channel, the scan with one; `lim` records may be written, and
+// with lim == 0 nothing may be, so emit is skipped and out[0] = n_total is all the caller gets.  The library (cwslg_fetch_decodes) and the
+// stand-alone check of the kernel (tests/harvest_kernel_check.hip) both launch through here.  The caller asks hipGetLastError.
+inline void harvest_launch(hipStream_t s, const HarvestDesc *d_desc, unsigned *d_counts, unsigned *d_offsets, unsigned *d_out, int n_chan, int lim, int ft4)
+{
+    for (int mode : {HARVEST_COUNT, HARVEST_SCAN, HARVEST_EMIT}) {
+        if (mode == HARVEST_EMIT && lim == 0) break;
+        hipLaunchKernelGGL(decode_harvest_kernel, dim3(mode == HARVEST_SCAN ? 1u : (unsigned)n_chan), dim3(HARVEST_NT), 0, s, d_desc, d_counts, d_offsets, d_out,
+                           n_chan, lim, ft4 ? 1 : 0, mode);
+    }
+}
+
 } // namespace cwslg

@@ -1034,11 +1034,7 @@ int cwslg_fetch_decodes(cwslg_ctx *c, int group, uint64_t *start_epoch, cwslg_de
     unsigned *d_out = (unsigned *)(hs.d + pad(desc_bytes) + 2 * cnt_bytes);
     HIPCHK(c, hipStreamWaitEvent(rf.fs, rf.ev, 0));
     HIPCHK(c, hipMemcpyAsync(hs.d, hs.h, desc_bytes, hipMemcpyHostToDevice, rf.fs));
-    for (int mode : {HARVEST_COUNT, HARVEST_SCAN, HARVEST_EMIT}) {
-        if (mode == HARVEST_EMIT && lim == 0) break;               // nothing may be written: the total is all the caller gets
-        hipLaunchKernelGGL(decode_harvest_kernel, dim3(mode == HARVEST_SCAN ? 1u : (unsigned)nch), dim3(HARVEST_NT), 0, rf.fs, d_desc, d_counts, d_offsets, d_out,
-                           (int)nch, (int)lim, ft4 ? 1 : 0, mode);
-    }
+    harvest_launch(rf.fs, d_desc, d_counts, d_offsets, d_out, (int)nch, (int)lim, ft4 ? 1 : 0);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(h_out, d_out, out_bytes, hipMemcpyDeviceToHost, rf.fs));
     HIPCHK(c, hipStreamSynchronize(rf.fs));

@@ -11,6 +11,7 @@ import pytest
 
 import decodes_ref as DR
 import harvest_cases as H
+import harvest_twin_cases as T
 import ldpc_cases as LC
 import record_race_cases as RC
 
@@ -128,6 +129,30 @@ def test_against_the_cpu_chain(xctx, mode, n_chan, osd, max_cand):
         assert again[1:] == (E, n_total, n_ch) and again[0].tobytes() == got.tobytes()
     if max_cand == 100 and n_chan == 2 and osd:
         assert total > 0 and (mode == "FT4" or got["ndup"].max() > 1)    # (the slots do contain what they were made for: test_harvest_inputs.py)
+
+
+@pytest.mark.parametrize("osd", [True, False], ids=["osd", "no_osd"])
+def test_ft4_twins_against_the_cpu_chain(xctx, osd):
+    """FT4 de-duplication and its rank decisions on real slots: harvest_twin_cases sends one message at two or three audio frequencies of a
+    channel, so that one word sits on two BP records with unequal nharderr, on an OSD record with a smaller entry than the BP record that is
+    reported, on two OSD records, and on three records (tests/test_harvest_twin_inputs.py proves it).  The call equals decodes_ref on the CPU
+    chain's records, with OSD on and off, and the per-channel fetches return the same bytes before and after it."""
+    mode = "FT4"
+    g = _Group(xctx, mode, T.RF, T.MAX_CAND, osd=osd)
+    ndup = 0
+    for e in range(T.N_EPOCHS):
+        iq, step = T.slot_iq(e), 64 * T.BLK
+        for k in range(0, len(iq), step):
+            xctx.push_iq(g.rx, iq[k:k + step])
+        xctx.slot_boundary(mode, T.start_epoch(e + 1))
+        before = _own_bytes(xctx, mode, g.chans)
+        want, total = T.expected(g.chans, e, osd=osd)
+        got, E, n_total, n_ch = xctx.fetch_decodes(mode, 0, BIG)
+        assert (E, n_total, n_ch) == (T.start_epoch(e), total, 2), (e, E, n_total, n_ch, total)
+        _same(got, want)
+        assert _own_bytes(xctx, mode, g.chans) == before
+        ndup = max(ndup, int(got["ndup"].max()))
+    assert ndup >= 3
 
 
 # ---- truncation ------------------------------------------------------------------------------------------------------------------------------------

@@ -57,8 +57,9 @@ def test_ft8_slots_differ_and_cut_lists_differ_too():
 
 def test_ft4_slots():
     """record_race_cases' first three FT4 slots: decodes on both channels in every slot, words from a set other than 0, a word by OSD -- and no
-    word on two sync records: none was found in these slots nor in the recipe family of ft4_decode_cases (one burst moved through the slot in
-    0.1 s steps at two amplitudes), so FT4 de-duplication rests on tests/test_decodes_ref.py."""
+    word on two sync records: none is found in these slots nor in the recipe family of ft4_decode_cases (one burst moved through the slot in
+    0.1 s steps at two amplitudes).  FT4 de-duplication runs on the GPU on the slots of tests/harvest_twin_cases.py, which send one message at
+    several audio frequencies, and on the synthetic records of tests/harvest_kernel_cases.py."""
     sets, by_osd, dups = set(), 0, 0
     for e in range(H.N_EPOCHS):
         for k in range(2):
