@@ -154,6 +154,16 @@ DECODE_DTYPE = np.dtype([("ch_id", np.int32), ("entry", np.int16), ("by_osd", np
 assert DECODE_DTYPE.itemsize == 40
 
 
+class DecodeReport(C.Structure):
+    """cwslg_decode_report (16 bytes): the signal report of one cwslg_decode."""
+    _fields_ = [("snr_db", C.c_float), ("xsig", C.c_float), ("xnoise", C.c_float), ("nsync", C.c_int16), ("nsymerr", C.c_int16)]
+
+
+# numpy view of cwslg_decode_report, as cwslg_fetch_decode_reports hands them out: record p belongs to decode p
+DECODE_REPORT_DTYPE = np.dtype([("snr_db", np.float32), ("xsig", np.float32), ("xnoise", np.float32), ("nsync", np.int16), ("nsymerr", np.int16)])
+assert DECODE_REPORT_DTYPE.itemsize == 16 == C.sizeof(DecodeReport)
+
+
 class Ft4Soft(C.Structure):
     _fields_ = [("llr", (C.c_float * 174) * 3), ("sigma", C.c_float * 3), ("nsync", C.c_int32), ("nqual", C.c_int32), ("pad_", C.c_int32)]
 
@@ -202,6 +212,7 @@ ABI_SYMBOLS = [
     "cwslg_set_ldpc_code", "cwslg_enable_ft8_decode", "cwslg_fetch_ft8_decode", "cwslg_ldpc_decode",
     "cwslg_enable_ft8_osd", "cwslg_fetch_ft8_osd", "cwslg_osd_decode", "cwslg_enable_ft4_decode", "cwslg_fetch_ft4_decode",
     "cwslg_enable_ft4_osd", "cwslg_fetch_ft4_osd", "cwslg_fetch_decodes",
+    "cwslg_fetch_decode_reports", "cwslg_ft8_tones",
     "cwslg_set_timing", "cwslg_demod_kernel_name", "cwslg_stream", "cwslg_channel_constants", "cwslg_phasor_checkpoint_stride", "cwslg_channel_phasor_checkpoints",
     "cwslg_slot_clock_next", "cwslg_pool_sizing", "cwslg_find_band", "cwslg_parse_decode_line",
     "cwslg_decoder_block_bytes", "cwslg_decoder_block_field", "cwslg_fill_decoder_block", "cwslg_decoder_route", "cwslg_decoder_command",
@@ -303,6 +314,8 @@ def load_library(build_if_missing=True):
     L.cwslg_enable_ft4_osd.argtypes = [vp, i32, i32, i32, i32]
     L.cwslg_fetch_ft4_osd.argtypes = [vp, i32, C.POINTER(Ft4Osd), i32, C.POINTER(i32), C.POINTER(u64)]
     L.cwslg_fetch_decodes.argtypes = [vp, i32, C.POINTER(u64), vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    L.cwslg_fetch_decode_reports.argtypes = [vp, i32, C.POINTER(u64), vp, vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    L.cwslg_ft8_tones.argtypes = [vp, vp, vp]
     L.cwslg_sync_debug_fetch.argtypes = [vp, i32, i32, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(i32)]
     L.cwslg_get_stats.argtypes = [vp, C.POINTER(Stats)]
     L.cwslg_reset_stats.argtypes = [vp]
@@ -817,6 +830,30 @@ class Context:
             return None
         self._chk(rc)
         return buf[:n.value].copy(), t0.value, n_total.value, n_ch.value
+
+    def fetch_decode_reports(self, group="FT8", start_epoch=0, max=4096):
+        """cwslg_fetch_decode_reports: fetch_decodes with a signal report per decode (FT8 group only; needs a systematic code loaded).  -> None if
+        no channel takes part, else (records, reports, start_epoch, n_total, n_channels): reports a numpy array (DECODE_REPORT_DTYPE), reports[p]
+        the SNR figure, xsig / xnoise and the nsync / nsymerr tone checks of records[p]."""
+        g = (GROUPS[group] if group in GROUPS else _MODE_GROUP[group]) if isinstance(group, str) else int(group)
+        m = int(max)
+        dec, rep = np.zeros(m if m > 1 else 1, DECODE_DTYPE), np.zeros(m if m > 1 else 1, DECODE_REPORT_DTYPE)
+        t0, n, n_total, n_ch = C.c_uint64(int(start_epoch)), C.c_int(), C.c_int(), C.c_int()
+        rc = self.L.cwslg_fetch_decode_reports(self.h, g, C.byref(t0), dec.ctypes.data if m > 0 else None, rep.ctypes.data if m > 0 else None, m,
+                                               C.byref(n), C.byref(n_total), C.byref(n_ch))
+        if rc == ERR_NO_FRAME:
+            return None
+        self._chk(rc)
+        return dec[:n.value].copy(), rep[:n.value].copy(), t0.value, n_total.value, n_ch.value
+
+    def ft8_tones(self, bits):
+        """cwslg_ft8_tones: the 79 channel tones of a 91-bit word (bits[12] as in a decode record) under the code in force -> uint8[79]."""
+        b = np.ascontiguousarray(np.frombuffer(bytes(bits), np.uint8) if isinstance(bits, (bytes, bytearray)) else np.asarray(bits, np.uint8))
+        if b.shape != (12,):
+            raise ValueError("bits: 12 bytes")
+        tones = np.zeros(79, np.uint8)
+        self._chk(self.L.cwslg_ft8_tones(self.h, b.ctypes.data, tones.ctypes.data))
+        return tones
 
     def enable_long_sync(self, on=True, nfa_hz=1400, nfb_hz=1600, minsync=1.2):
         """Candidate search of the 120 s modes (WSPR: wsprd's front end; FST4W-120: get_candidates_fst4 over nfa..nfb)."""

@@ -13,18 +13,27 @@
 // thereby in ascending entry order: 12-byte key, rank (by_osd, nharderr, entry) in one word, (slot, set) in another.  Every listed word then
 // looks for equal keys -- counting them (ndup) and giving way to a better rank -- and a third ballot pass numbers the survivors.  Integer work
 // only; every global address goes through the global address space; no register array is indexed.
+//
+// cwslg_fetch_decode_reports adds a fourth mode of the same symbol, launched ONCE behind the three above (FT8 only):
+//   HARVEST_REPORT grid (ceil(min(n_total, max_out) / 4)): one WAVE per emitted record, no workgroup barrier -> the 16-byte cwslg_decode_report
+// of record p: the word is re-encoded (91 bits -> 174 -> 79 tones) with the systematic encoder of the loaded code and the channel's symbol-spectra
+// plane is read at the candidate's grid position, with ft8_softbits_kernel's addressing.  The arithmetic is the header's (cwslg_decode_report),
+// restated in tests/decode_reports_ref.py, bit for bit: this translation unit is built -ffp-contract=off.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "sync_kernels.hpp"
+#include "ft8soft_kernels.hpp"
 
 namespace cwslg {
 
-constexpr int HARVEST_COUNT = 0, HARVEST_SCAN = 1, HARVEST_EMIT = 2;
+constexpr int HARVEST_COUNT = 0, HARVEST_SCAN = 1, HARVEST_EMIT = 2, HARVEST_REPORT = 3;
 constexpr int HARVEST_NT = 256;
 constexpr int HARVEST_MAXSLOTS = 3 * SYNC_MAXCAND_CAP;                  // FT4: three record slots per candidate
 constexpr int HARVEST_REC_WORDS = 10;                                   // cwslg_decode is 40 bytes
 constexpr int HARVEST_HEAD_WORDS = 4;                                   // out[0] = n_total; the records follow 16 bytes in
+constexpr int REPORT_WORDS = 4;                                         // cwslg_decode_report is 16 bytes
+constexpr int REPORT_ENC_ROWS = 91, REPORT_ENC_WORDS = 6;               // the encoder: OsdGen (ldpc_host.hpp), 91 rows of 6 dwords
 
 // One channel that takes part, built by the host under the context mutex.
 struct alignas(16) HarvestDesc {
@@ -37,6 +46,17 @@ struct alignas(16) HarvestDesc {
     int ch_id;
 };
 static_assert(sizeof(HarvestDesc) == 48, "descriptor layout");
+
+// What the report mode needs of the same channel, in an array of its own beside the HarvestDesc array (same index).
+struct alignas(16) ReportDesc {
+    const float *spectra;    // the channel's symbol-spectra plane, [372][nbins]
+    const void *list;        // Cand[cap]
+    int nbins;               // row pitch of the plane
+    int pad_[3];
+};
+static_assert(sizeof(ReportDesc) == 32, "descriptor layout");
+struct ReportRec { float snr_db, xsig, xnoise; int16_t nsync, nsymerr; };       // = cwslg_decode_report
+static_assert(sizeof(ReportRec) == REPORT_WORDS * sizeof(unsigned), "cwslg_decode_report is 16 bytes");
 
 // Ordered compaction over the workgroup: the number of flagged threads before this one (threads in ascending tid); *total = all of them.
 // s_w: 4 words of LDS; two barriers.
@@ -53,15 +73,150 @@ __device__ __forceinline__ unsigned harvest_place(bool flag, unsigned *s_w, unsi
     return before + (wave > 0 ? w0 : 0u) + (wave > 1 ? w1 : 0u) + (wave > 2 ? w2 : 0u);
 }
 
+// ---- HARVEST_REPORT ------------------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ unsigned report_pick6(unsigned w0, unsigned w1, unsigned w2, unsigned w3, unsigned w4, unsigned w5, int i)
+{
+    return i == 0 ? w0 : i == 1 ? w1 : i == 2 ? w2 : i == 3 ? w3 : i == 4 ? w4 : w5;
+}
+
+// the tone of symbol n (0..78) of the codeword c0..c5 (OsdGen bit layout); *costas: n is a Costas symbol
+__device__ __forceinline__ int report_tone(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned c4, unsigned c5, int n, bool *costas)
+{
+    const int blk = n < 36 ? 0 : n < 72 ? 1 : 2, r = n - 36 * blk;
+    *costas = r < 7;
+    const int icos7 = (0x2560413 >> (4 * (r < 7 ? r : 0))) & 7;        // 3,1,4,0,6,5,2
+    const int d = n - (n < 36 ? 7 : 14);                                // data symbol 0..57 (meaningless for a Costas symbol: clamped)
+    const int t = 3 * (d < 0 ? 0 : d > 57 ? 57 : d), wi = t >> 5;
+    const unsigned lo = report_pick6(c0, c1, c2, c3, c4, c5, wi), hi = report_pick6(c1, c2, c3, c4, c5, 0u, wi);
+    const unsigned x = (unsigned)((((unsigned long long)hi << 32) | lo) >> (t & 31)) & 7u;      // cw[3d] | cw[3d+1] << 1 | cw[3d+2] << 2
+    const unsigned v = (x & 1u) << 2 | (x & 2u) | x >> 2;
+    const int gray = (0x74652310 >> (4 * v)) & 7;                       // graymap 0,1,3,2,5,6,4,7
+    return r < 7 ? icos7 : gray;
+}
+
+// One symbol of the wave's power image: first maximum of the magnitudes at the encoded tone?  the power at the tone and at (tone + 4) mod 7
+__device__ __forceinline__ bool report_symbol(const float *pw, int n, int tone, float *sig, float *noi)
+{
+    const v4f lo = *reinterpret_cast<const v4f *>(pw + 8 * n), hi = *reinterpret_cast<const v4f *>(pw + 8 * n + 4);
+    const float s0 = sqrtf(lo.x), s1 = sqrtf(lo.y), s2 = sqrtf(lo.z), s3 = sqrtf(lo.w), s4 = sqrtf(hi.x), s5 = sqrtf(hi.y), s6 = sqrtf(hi.z), s7 = sqrtf(hi.w);
+    int km = 0;
+    float vm = s0;
+    if (s1 > vm) { vm = s1; km = 1; }
+    if (s2 > vm) { vm = s2; km = 2; }
+    if (s3 > vm) { vm = s3; km = 3; }
+    if (s4 > vm) { vm = s4; km = 4; }
+    if (s5 > vm) { vm = s5; km = 5; }
+    if (s6 > vm) { vm = s6; km = 6; }
+    if (s7 > vm) { vm = s7; km = 7; }
+    const int u = tone + 4;
+    *sig = pw[8 * n + tone];
+    *noi = pw[8 * n + (u >= 7 ? u - 7 : u)];
+    return km == tone;
+}
+
+// One wave per emitted record.  s_pw: the wave's [80][8] image of powers (2560 bytes of the workgroup's LDS, private to the wave).
+__device__ __forceinline__ void harvest_report_wave(const ReportDesc *rdesc, const unsigned *offsets, const unsigned *out, const uint32_t *enc,
+                                                    unsigned *rep, int n_chan, int max_out, float *s_pw)
+{
+    typedef unsigned v2u __attribute__((ext_vector_type(2)));
+    typedef unsigned v4u __attribute__((ext_vector_type(4)));
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const CWSLG_GLOBAL unsigned *g_out = as_global(out), *g_offsets = as_global(offsets);
+    const unsigned n_emit = min((unsigned)__builtin_amdgcn_readfirstlane((int)g_out[0]), (unsigned)max(max_out, 0));
+    const unsigned p = blockIdx.x * (unsigned)FT8S_WAVES + (unsigned)wv;
+    if (p >= n_emit) return;                                    // wave-uniform
+    // the record's channel: the last c with offsets[c] <= p (offsets[0] = 0; channels without decodes make equal offsets)
+    int lo_c = 0, hi_c = n_chan;
+    while (hi_c - lo_c > 1) {
+        const int mid = (lo_c + hi_c) >> 1;
+        const unsigned o = (unsigned)__builtin_amdgcn_readfirstlane((int)g_offsets[mid]);
+        if (o <= p) lo_c = mid; else hi_c = mid;
+    }
+    const CWSLG_GLOBAL ReportDesc *rd = as_global(rdesc) + lo_c;
+    const CWSLG_GLOBAL unsigned *rec = g_out + HARVEST_HEAD_WORDS + (size_t)p * HARVEST_REC_WORDS;
+    const unsigned entry = rec[1] & 0xffffu, k0 = rec[2], k1 = rec[3], k2 = rec[4];
+    const CWSLG_GLOBAL int *cd = as_global(reinterpret_cast<const int *>(rd->list)) + (size_t)entry * 5u;     // Cand: freq_bin, time_step, ...
+    const int i = cd[0], j = cd[1], nbins = rd->nbins;
+    const CWSLG_GLOBAL float *spec = as_global(rd->spectra);
+
+    // ---- the plane: ft8_softbits_kernel's 20 passes of 4 symbols x 16 bins, all loads in flight before anything else waits ----
+    const int sub = lane >> 4, c = lane & 15;
+    const int bin = i + c;
+    const bool col_ok = c < 15 && bin >= 0 && bin <= FT8_NH1 && bin < nbins;
+    float pv[20];
+#pragma unroll
+    for (int ps = 0; ps < 20; ++ps) {
+        const int n = 4 * ps + sub;
+        const int m = j + 12 + 4 * n;                          // 1-based symbol step
+        const bool ok = col_ok && n < FT8S_NSYM && m >= 1 && m <= FT8_NHSYM;
+        // (an element outside the plane fetches element 0 and drops it: no load under a condition)
+        const float v = spec[ok ? (size_t)(m - 1) * (size_t)nbins + (size_t)bin : (size_t)0];
+        pv[ps] = ok ? v : 0.0f;
+    }
+
+    // ---- the codeword: lane l owns encoder rows l and l + 64 (rows 64..90 on lanes 0..26); XOR across the lanes ----
+    const int row_b = lane + 64 < REPORT_ENC_ROWS ? lane + 64 : lane;  // (a lane without a second row loads its first again and drops it)
+    const CWSLG_GLOBAL v2u *ea = reinterpret_cast<const CWSLG_GLOBAL v2u *>(as_global(enc) + (size_t)lane * REPORT_ENC_WORDS);
+    const CWSLG_GLOBAL v2u *eb = reinterpret_cast<const CWSLG_GLOBAL v2u *>(as_global(enc) + (size_t)row_b * REPORT_ENC_WORDS);
+    const v2u a0 = ea[0], a1 = ea[1], a2 = ea[2], b0 = eb[0], b1 = eb[1], b2 = eb[2];
+    // message bit k: byte k >> 3 of bits[12] (three little-endian words), MSB first
+    const unsigned wa = lane < 32 ? k0 : k1;                                        // k = lane: bytes 0..7
+    const unsigned bit_a = wa >> (8 * ((lane >> 3) & 3) + 7 - (lane & 7)) & 1u;
+    const unsigned bit_b = lane + 64 < REPORT_ENC_ROWS ? k2 >> (8 * ((lane >> 3) & 3) + 7 - (lane & 7)) & 1u : 0u;     // k = lane + 64: bytes 8..11
+    const unsigned ma = 0u - bit_a, mb = 0u - bit_b;
+    unsigned c0 = (a0.x & ma) ^ (b0.x & mb), c1 = (a0.y & ma) ^ (b0.y & mb), c2 = (a1.x & ma) ^ (b1.x & mb);
+    unsigned c3 = (a1.y & ma) ^ (b1.y & mb), c4 = (a2.x & ma) ^ (b2.x & mb), c5 = (a2.y & ma) ^ (b2.y & mb);
+#pragma unroll
+    for (int h = 32; h >= 1; h >>= 1) {
+        c0 ^= (unsigned)__shfl_xor((int)c0, h, 64); c1 ^= (unsigned)__shfl_xor((int)c1, h, 64); c2 ^= (unsigned)__shfl_xor((int)c2, h, 64);
+        c3 ^= (unsigned)__shfl_xor((int)c3, h, 64); c4 ^= (unsigned)__shfl_xor((int)c4, h, 64); c5 ^= (unsigned)__shfl_xor((int)c5, h, 64);
+    }
+
+    // ---- the image of powers, private to this wave ----
+    if (!(c & 1) && c < 15) {
+#pragma unroll
+        for (int ps = 0; ps < 20; ++ps) s_pw[8 * (4 * ps + sub) + (c >> 1)] = pv[ps];
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+
+    // ---- lane l: symbol l, and symbol l + 64 where that is below 79 ----
+    const bool two = lane + 64 < FT8S_NSYM;
+    const int nb = two ? lane + 64 : lane;
+    bool cos_a, cos_b;
+    const int ta = report_tone(c0, c1, c2, c3, c4, c5, lane, &cos_a), tb = report_tone(c0, c1, c2, c3, c4, c5, nb, &cos_b);
+    float sig_a, noi_a, sig_b, noi_b;
+    const bool hit_a = report_symbol(s_pw, lane, ta, &sig_a, &noi_a), hit_b = report_symbol(s_pw, nb, tb, &sig_b, &noi_b);
+    const int nsync = __popcll(__ballot(cos_a && hit_a)) + __popcll(__ballot(two && cos_b && hit_b));
+    const int nsymerr = __popcll(__ballot(!cos_a && !hit_a)) + __popcll(__ballot(two && !cos_b && !hit_b));
+    const float xsig = ft8s_tree64(two ? sig_a + sig_b : sig_a), xnoise = ft8s_tree64(two ? noi_a + noi_b : noi_a);
+    if (lane == 0) {
+        const float r = xnoise > 0.0f ? xsig / xnoise - 1.0f : 0.0f;
+        const float x = fminf(r > 0.1f ? r : 0.001f, 3.4028234663852886e38f);      // (an infinite ratio reports as the largest float's)
+        const float db = (float)(10.0 * long_log10_fixed((double)x) - 27.0);
+        v4u o;
+        o.x = __float_as_uint(fmaxf(db, -24.0f)); o.y = __float_as_uint(xsig); o.z = __float_as_uint(xnoise);
+        o.w = (unsigned)nsync | (unsigned)nsymerr << 16;
+        *reinterpret_cast<CWSLG_GLOBAL v4u *>(as_global_rw(rep) + (size_t)p * REPORT_WORDS) = o;
+    }
+}
+
 __global__ __launch_bounds__(HARVEST_NT) void decode_harvest_kernel(const HarvestDesc *__restrict__ desc, unsigned *__restrict__ counts,
                                                                     unsigned *__restrict__ offsets, unsigned *__restrict__ out, int n_chan, int max_out,
-                                                                    int ft4, int mode)
+                                                                    int ft4, int mode, const ReportDesc *__restrict__ rdesc,
+                                                                    const uint32_t *__restrict__ enc, unsigned *__restrict__ rep)
 {
-    __shared__ unsigned s_key[3][HARVEST_MAXSLOTS];      // the word: bits[12] as three little-endian words
+    __shared__ __attribute__((aligned(16))) unsigned s_key[3][HARVEST_MAXSLOTS];      // the word: bits[12] as three little-endian words; HARVEST_REPORT: four waves' power images
     __shared__ unsigned s_rank[HARVEST_MAXSLOTS];        // by_osd << 28 | nharderr << 16 | entry: smaller is better, never equal
     __shared__ unsigned s_info[HARVEST_MAXSLOTS];        // slot | set << 12; after the de-duplication: | ndup << 16 | survivor << 15
     __shared__ unsigned s_w[4];
     const unsigned tid = threadIdx.x;
+    if (mode == HARVEST_REPORT) {
+        static_assert(FT8S_WAVES * 64 == HARVEST_NT && FT8S_WAVES * (FT8S_NSYM + 1) * 8 <= 3 * HARVEST_MAXSLOTS, "four power images fit s_key");
+        harvest_report_wave(rdesc, offsets, out, enc, rep, n_chan, max_out, reinterpret_cast<float *>(&s_key[0][0]) + (tid >> 6) * ((FT8S_NSYM + 1) * 8));
+        return;
+    }
     CWSLG_GLOBAL unsigned *g_counts = as_global_rw(counts), *g_offsets = as_global_rw(offsets), *g_out = as_global_rw(out);
 
     if (mode == HARVEST_SCAN) {
@@ -209,8 +364,19 @@ inline void harvest_launch(hipStream_t s, const HarvestDesc *d_desc, unsigned *d
     for (int mode : {HARVEST_COUNT, HARVEST_SCAN, HARVEST_EMIT}) {
         if (mode == HARVEST_EMIT && lim == 0) break;
         hipLaunchKernelGGL(decode_harvest_kernel, dim3(mode == HARVEST_SCAN ? 1u : (unsigned)n_chan), dim3(HARVEST_NT), 0, s, d_desc, d_counts, d_offsets, d_out,
-                           n_chan, lim, ft4 ? 1 : 0, mode);
+                           n_chan, lim, ft4 ? 1 : 0, mode, (const ReportDesc *)nullptr, (const uint32_t *)nullptr, (unsigned *)nullptr);
     }
+}
+
+// The ONE further launch of cwslg_fetch_decode_reports, behind harvest_launch on the same stream and blocks: a wave per record that emit may have
+// written (the count, min(out[0], lim), is read on the device; the waves beyond it leave), the reports to d_rep[lim][4].  Nothing to launch for
+// lim == 0.  d_enc: the encoder's 91 x 6 dwords.  The library and tests/report_kernel_check.hip both launch through here.
+inline void report_launch(hipStream_t s, const ReportDesc *d_rdesc, const unsigned *d_offsets, const unsigned *d_out, const uint32_t *d_enc, unsigned *d_rep,
+                          int n_chan, int lim)
+{
+    if (lim <= 0) return;
+    hipLaunchKernelGGL(decode_harvest_kernel, dim3((unsigned)((lim + FT8S_WAVES - 1) / FT8S_WAVES)), dim3(HARVEST_NT), 0, s, (const HarvestDesc *)nullptr,
+                       (unsigned *)nullptr, const_cast<unsigned *>(d_offsets), const_cast<unsigned *>(d_out), n_chan, lim, 0, HARVEST_REPORT, d_rdesc, d_enc, d_rep);
 }
 
 } // namespace cwslg

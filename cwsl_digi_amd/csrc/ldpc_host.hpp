@@ -148,6 +148,59 @@ inline int ldpc_generator(const LdpcTables &t, OsdGen *gen)
     return rank;
 }
 
+// ---- re-encoding (cwslg_decode_report in include/cwsl_gpu.h; tests/decode_reports_ref.py restates it) ----------------------------------------------
+// The systematic encoder of the loaded code in the OsdGen layout: row k (k = 0..90) is the codeword of the unit message e_k -- bit k, and the parity
+// bits 91..173 that H demands.  H is reduced taking pivots in columns 91..173 only; false (and *enc untouched) when those 83 columns are singular:
+// such a table is still a code the decoders take, but a 91-bit word then has no codeword that merely continues it.
+inline bool ldpc_encoder(const LdpcTables &t, OsdGen *enc)
+{
+    uint32_t h[LDPC_M][OSD_GW];
+    memset(h, 0, sizeof(h));
+    for (int m = 0; m < LDPC_M; ++m)
+        for (int e = 0; e < LDPC_ROWMAX; ++e)
+            if (t.rowbit[m][e] != LDPC_ABSENT) h[m][t.rowbit[m][e] >> 5] ^= 1u << (t.rowbit[m][e] & 31);
+    for (int r = 0; r < LDPC_M; ++r) {                         // reduced row r ends up with column 91 + r alone among the parity columns
+        const int c = LDPC_K + r;
+        int p = r;
+        while (p < LDPC_M && !((h[p][c >> 5] >> (c & 31)) & 1u)) ++p;
+        if (p == LDPC_M) return false;
+        for (int w = 0; w < OSD_GW; ++w) { const uint32_t x = h[p][w]; h[p][w] = h[r][w]; h[r][w] = x; }
+        for (int i = 0; i < LDPC_M; ++i)
+            if (i != r && ((h[i][c >> 5] >> (c & 31)) & 1u))
+                for (int w = 0; w < OSD_GW; ++w) h[i][w] ^= h[r][w];
+    }
+    if (!enc) return true;
+    memset(enc, 0, sizeof(*enc));
+    for (int k = 0; k < LDPC_K; ++k) {
+        enc->row[k][k >> 5] |= 1u << (k & 31);
+        for (int r = 0; r < LDPC_M; ++r)                       // parity bit 91 + r of e_k: the entry of reduced row r in column k
+            if ((h[r][k >> 5] >> (k & 31)) & 1u) enc->row[k][(LDPC_K + r) >> 5] |= 1u << ((LDPC_K + r) & 31);
+    }
+    return true;
+}
+
+// The 174-bit codeword (OsdGen bit layout) of the 91 message bits of bits[12] (MSB first, as cwslg_ft8_msg.bits; the last 5 bits are ignored)
+inline void ldpc_encode(const OsdGen &enc, const uint8_t *bits, uint32_t *cw)
+{
+    for (int w = 0; w < OSD_GW; ++w) cw[w] = 0;
+    for (int k = 0; k < LDPC_K; ++k)
+        if ((bits[k >> 3] >> (7 - (k & 7))) & 1)
+            for (int w = 0; w < OSD_GW; ++w) cw[w] ^= enc.row[k][w];
+}
+
+// The 79 channel tones of a codeword: Costas 3,1,4,0,6,5,2 at symbols 0..6, 36..42, 72..78; data symbol d (0..57) at n = d + 7 (d < 29) or
+// d + 14, its tone graymap[4 cw[3d] + 2 cw[3d+1] + cw[3d+2]] -- the inverse of what ft8_softbits_kernel reads.
+inline void ft8_tones_of(const uint32_t *cw, uint8_t *tones)
+{
+    static const uint8_t icos7[7] = {3, 1, 4, 0, 6, 5, 2}, graymap[8] = {0, 1, 3, 2, 5, 6, 4, 7};
+    for (int r = 0; r < 7; ++r) tones[r] = tones[36 + r] = tones[72 + r] = icos7[r];
+    for (int d = 0; d < 58; ++d) {
+        unsigned v = 0;
+        for (int b = 0; b < 3; ++b) v = (v << 1) | ((cw[(3 * d + b) >> 5] >> ((3 * d + b) & 31)) & 1u);
+        tones[d + (d < 29 ? 7 : 14)] = graymap[v];
+    }
+}
+
 // d(c) of the contract: float32 adds of a[t] over the set bits of the error pattern, ascending t
 inline float osd_distance(const uint32_t *e, const float *a)
 {

@@ -453,19 +453,7 @@ __global__ __launch_bounds__(256) void wspr_spectra_kernel(const LongWork *__res
     }
 }
 
-__device__ __forceinline__ double long_log10_fixed(double x)          // = orc_log10_fixed (oracle/sync_oracle.c)
-{
-    if (!(x > 0.0)) return -1.0e300;
-    int e = 0;
-    double m = x;
-    while (m >= 1.4142135623730951) { m = m * 0.5; ++e; }
-    while (m < 0.7071067811865476) { m = m * 2.0; --e; }
-    const double t = (m - 1.0) / (m + 1.0), t2 = t * t;
-    double s = 0.0;
-    for (int k = 21; k >= 1; k -= 2) s = s * t2 + 1.0 / (double)k;
-    const double ln_m = 2.0 * t * s;
-    return ((double)e * 0.6931471805599453 + ln_m) * 0.4342944819032518;
-}
+// (long_log10_fixed: sync_kernels.hpp, which the translation unit includes first -- the decode reports of harvest_kernels.hpp use it too)
 
 // psavg -> smspec -> noise percentile -> peaks -> snr -> +-110 Hz -> order by snr (stable, descending).  grid (channels), 512 threads.
 __global__ __launch_bounds__(512) void wspr_peaks_kernel(const LongWork *__restrict__ works)

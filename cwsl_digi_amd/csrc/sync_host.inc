@@ -771,6 +771,15 @@ int cwslg_set_ldpc_code(cwslg_ctx *c, const uint8_t *nm)
     HIPCHK(c, hipMemcpy(c->sync_shared.d_ldpc, &t, sizeof(LdpcTables), hipMemcpyHostToDevice));
     c->sync_shared.ldpc_loaded = true;
     c->sync_shared.osd_ready = false;
+    // the systematic encoder of the decode reports: host bytes only (the device copy is made by the first cwslg_fetch_decode_reports after this
+    // load); a table whose columns 91..173 are singular is still a code the decoders take, it merely has no reports
+    {
+        OsdGen enc;
+        c->sync_shared.enc_ready = ldpc_encoder(t, &enc);
+        c->sync_shared.enc_dirty = c->sync_shared.enc_ready;
+        static_assert(sizeof(c->sync_shared.enc_gen) == sizeof(OsdGen), "encoder block");
+        if (c->sync_shared.enc_ready) std::memcpy(c->sync_shared.enc_gen, &enc, sizeof(OsdGen));
+    }
     if (full_rank) {
         static_assert(sizeof(c->sync_shared.osd_gen) == sizeof(OsdGen), "generator block");
         std::memcpy(c->sync_shared.osd_gen, &gen, sizeof(OsdGen));
@@ -961,23 +970,27 @@ int cwslg_fetch_ft4_osd(cwslg_ctx *c, int ch_id, cwslg_ft4_osd *dst, int max, in
 // under the context mutex, one ticket of the group, the work on a fetch stream behind the group's generation event with the mutex released --
 // except that what runs on the fetch stream is a descriptor upload, decode_harvest_kernel (count, scan, emit) and ONE copy down.  It writes only
 // the group's HarvestStage: no record, list, stamp or statistic changes.
-int cwslg_fetch_decodes(cwslg_ctx *c, int group, uint64_t *start_epoch, cwslg_decode *dst, int max, int *n, int *n_total, int *n_channels)
+// reports (cwslg_fetch_decode_reports, FT8 only): a ReportDesc per channel goes up behind the HarvestDesc array in the same copy, ONE further
+// launch (report_launch) follows the three, and the reports come down behind the records in the same copy.
+static int fetch_decodes_impl(cwslg_ctx *c, int group, uint64_t *start_epoch, cwslg_decode *dst, cwslg_decode_report *rep, int max, int *n, int *n_total,
+                              int *n_channels, bool reports)
 {
     static_assert(sizeof(cwslg_decode) == HARVEST_REC_WORDS * sizeof(unsigned), "record layout");
-    if (n) *n = 0;
-    if (n_total) *n_total = 0;
-    if (n_channels) *n_channels = 0;
-    if (!c || !start_epoch || !n || !n_total || (max > 0 && !dst)) return CWSLG_ERR_ARG;
-    if (group != CWSLG_GROUP_FT8 && group != CWSLG_GROUP_FT4) return fail(c, CWSLG_ERR_ARG, "decodes exist for the FT8 and FT4 groups only (group %d)", group);
+    static_assert(sizeof(cwslg_decode_report) == sizeof(ReportRec), "record layout");
     const bool ft4 = group == CWSLG_GROUP_FT4;
     const int k_msg = ft4 ? REC_MSG4 : REC_MSG8, k_osd = ft4 ? REC_OSD4 : REC_OSD8;
     HarvestStage &hs = c->harvest[ft4 ? 1 : 0];
     std::lock_guard<std::mutex> serial(hs.mu);
     std::vector<HarvestDesc> descs;
+    std::vector<ReportDesc> rdescs;
+    const uint32_t *d_enc = nullptr;
     size_t bound = 0;                   // no more decodes than entries
     ResultFetch rf;                     // ticket + lifetime, released when the copy is done or the call fails
     {
         std::lock_guard<std::mutex> g(c->mu);
+        if (reports && !c->sync_shared.enc_ready)
+            return fail(c, CWSLG_ERR_ARG, "%s", c->sync_shared.ldpc_loaded ? "decode reports need a systematic code: columns 91..173 of the loaded parity-check table are singular"
+                                                                    : "decode reports need a parity-check table (cwslg_set_ldpc_code)");
         uint64_t E = *start_epoch;
         std::vector<std::pair<int, uint64_t>> live;
         for (size_t id = 0; id < c->chans.size(); ++id) {
@@ -1002,19 +1015,40 @@ int cwslg_fetch_decodes(cwslg_ctx *c, int group, uint64_t *start_epoch, cwslg_de
             d.ch_id = l.first;
             descs.push_back(d);
             bound += (size_t)d.cap * (ft4 ? 3 : 1);
+            if (reports) {
+                ReportDesc r{};
+                r.spectra = b.d_spectra;
+                r.list = b.d_cand;
+                r.nbins = b.nbins;
+                rdescs.push_back(r);
+            }
         }
         if (descs.empty()) return CWSLG_ERR_NO_FRAME;
-        *start_epoch = E;
         hipSetDevice(c->device);
+        if (reports) {
+            // the encoder's device copy, made by the first call after a (re)load.  The report launches are its only readers; they belong to this
+            // group's calls, which hs.mu serialises and which synchronise before they return: none is in flight now
+            SyncShared &s = c->sync_shared;
+            if (!s.d_encgen) HIPCHK(c, hipMalloc(&s.d_encgen, sizeof(OsdGen)));
+            if (s.enc_dirty) {
+                HIPCHK(c, hipMemcpy(s.d_encgen, s.enc_gen, sizeof(OsdGen), hipMemcpyHostToDevice));
+                s.enc_dirty = false;
+            }
+            d_enc = (const uint32_t *)s.d_encgen;
+        }
+        *start_epoch = E;
         const int rc = begin_result_fetch(c, c->chans[descs[0].ch_id], rf);
         if (rc) return rc;
     }
     // no context lock from here on
     const size_t nch = descs.size(), lim = std::min((size_t)std::max(max, 0), bound);
     auto pad = [](size_t v) { return (v + 255) & ~size_t(255); };
-    const size_t desc_bytes = nch * sizeof(HarvestDesc), cnt_bytes = pad(nch * sizeof(unsigned));
-    const size_t out_bytes = (HARVEST_HEAD_WORDS + lim * HARVEST_REC_WORDS) * sizeof(unsigned);
-    const size_t h_need = pad(desc_bytes) + out_bytes, d_need = pad(desc_bytes) + 2 * cnt_bytes + out_bytes;
+    const size_t desc_bytes = nch * sizeof(HarvestDesc), rdesc_bytes = rdescs.size() * sizeof(ReportDesc), cnt_bytes = pad(nch * sizeof(unsigned));
+    const size_t up_bytes = reports ? pad(desc_bytes) + rdesc_bytes : desc_bytes, up_pad = pad(up_bytes);
+    // down: head | lim records | (reports: from the next 16-byte boundary) lim reports
+    const size_t rec_words = HARVEST_HEAD_WORDS + lim * HARVEST_REC_WORDS, rep_at = (rec_words + 3) & ~size_t(3);
+    const size_t out_bytes = (reports ? rep_at + lim * REPORT_WORDS : rec_words) * sizeof(unsigned);
+    const size_t h_need = up_pad + out_bytes, d_need = up_pad + 2 * cnt_bytes + out_bytes;
     if (hs.h_bytes < h_need) {
         if (hs.h) (void)hipHostFree(hs.h);
         hs.h = nullptr; hs.h_bytes = 0;
@@ -1028,21 +1062,62 @@ int cwslg_fetch_decodes(cwslg_ctx *c, int group, uint64_t *start_epoch, cwslg_de
         hs.d_bytes = pad(d_need + d_need / 2);
     }
     std::memcpy(hs.h, descs.data(), desc_bytes);
-    unsigned *h_out = (unsigned *)(hs.h + pad(desc_bytes));
+    if (reports) std::memcpy(hs.h + pad(desc_bytes), rdescs.data(), rdesc_bytes);
+    unsigned *h_out = (unsigned *)(hs.h + up_pad);
     const HarvestDesc *d_desc = (const HarvestDesc *)hs.d;
-    unsigned *d_counts = (unsigned *)(hs.d + pad(desc_bytes)), *d_offsets = (unsigned *)(hs.d + pad(desc_bytes) + cnt_bytes);
-    unsigned *d_out = (unsigned *)(hs.d + pad(desc_bytes) + 2 * cnt_bytes);
+    unsigned *d_counts = (unsigned *)(hs.d + up_pad), *d_offsets = (unsigned *)(hs.d + up_pad + cnt_bytes);
+    unsigned *d_out = (unsigned *)(hs.d + up_pad + 2 * cnt_bytes);
     HIPCHK(c, hipStreamWaitEvent(rf.fs, rf.ev, 0));
-    HIPCHK(c, hipMemcpyAsync(hs.d, hs.h, desc_bytes, hipMemcpyHostToDevice, rf.fs));
+    HIPCHK(c, hipMemcpyAsync(hs.d, hs.h, up_bytes, hipMemcpyHostToDevice, rf.fs));
     harvest_launch(rf.fs, d_desc, d_counts, d_offsets, d_out, (int)nch, (int)lim, ft4 ? 1 : 0);
+    if (reports) report_launch(rf.fs, (const ReportDesc *)(hs.d + pad(desc_bytes)), d_offsets, d_out, d_enc, d_out + rep_at, (int)nch, (int)lim);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(h_out, d_out, out_bytes, hipMemcpyDeviceToHost, rf.fs));
     HIPCHK(c, hipStreamSynchronize(rf.fs));
     const size_t total = h_out[0], got = std::min(total, lim);
-    if (got) std::memcpy(dst, h_out + HARVEST_HEAD_WORDS, got * sizeof(cwslg_decode));
+    if (got && dst) std::memcpy(dst, h_out + HARVEST_HEAD_WORDS, got * sizeof(cwslg_decode));
+    if (got && rep) std::memcpy(rep, h_out + rep_at, got * sizeof(cwslg_decode_report));
     *n = (int)got;
     *n_total = (int)total;
     if (n_channels) *n_channels = (int)nch;
+    return CWSLG_OK;
+}
+
+int cwslg_fetch_decodes(cwslg_ctx *c, int group, uint64_t *start_epoch, cwslg_decode *dst, int max, int *n, int *n_total, int *n_channels)
+{
+    if (n) *n = 0;
+    if (n_total) *n_total = 0;
+    if (n_channels) *n_channels = 0;
+    if (!c || !start_epoch || !n || !n_total || (max > 0 && !dst)) return CWSLG_ERR_ARG;
+    if (group != CWSLG_GROUP_FT8 && group != CWSLG_GROUP_FT4) return fail(c, CWSLG_ERR_ARG, "decodes exist for the FT8 and FT4 groups only (group %d)", group);
+    return fetch_decodes_impl(c, group, start_epoch, dst, nullptr, max, n, n_total, n_channels, false);
+}
+
+// The same call with a signal report per decode (harvest_kernels.hpp: HARVEST_REPORT; the contract is the header's, cwslg_decode_report).
+int cwslg_fetch_decode_reports(cwslg_ctx *c, int group, uint64_t *start_epoch, cwslg_decode *dec, cwslg_decode_report *rep, int max, int *n, int *n_total,
+                               int *n_channels)
+{
+    if (n) *n = 0;
+    if (n_total) *n_total = 0;
+    if (n_channels) *n_channels = 0;
+    if (!c || !start_epoch || !n || !n_total) return CWSLG_ERR_ARG;
+    if (group != CWSLG_GROUP_FT8) return fail(c, CWSLG_ERR_ARG, "decode reports exist for the FT8 group only (group %d)", group);
+    return fetch_decodes_impl(c, group, start_epoch, dec, rep, max, n, n_total, n_channels, true);
+}
+
+// The 79 channel tones of a 91-bit word under the code in force: the re-encoder of the reports on its own, host work only.
+int cwslg_ft8_tones(cwslg_ctx *c, const uint8_t *bits, uint8_t *tones)
+{
+    if (!c || !bits || !tones) return CWSLG_ERR_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    if (!c->sync_shared.enc_ready)
+        return fail(c, CWSLG_ERR_ARG, "%s", c->sync_shared.ldpc_loaded ? "no systematic code: columns 91..173 of the loaded parity-check table are singular"
+                                                                : "no parity-check table loaded (cwslg_set_ldpc_code)");
+    OsdGen enc;
+    std::memcpy(&enc, c->sync_shared.enc_gen, sizeof(OsdGen));
+    uint32_t cw[OSD_GW];
+    ldpc_encode(enc, bits, cw);
+    ft8_tones_of(cw, tones);
     return CWSLG_OK;
 }
 

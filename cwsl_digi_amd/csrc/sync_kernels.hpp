@@ -78,6 +78,10 @@ struct SyncShared {
     void *d_osdgen = nullptr;             // its device copy: allocated by the first cwslg_enable_ft8_osd / cwslg_enable_ft4_osd / cwslg_osd_decode, replaced by every later cwslg_set_ldpc_code
     bool osd_ready = false;               // the loaded code has rank 83: OSD may be enabled
     bool osd_dirty = false;               // osd_gen is newer than the device copy
+    uint32_t enc_gen[91 * 6] = {};        // the systematic encoder of the loaded code (ldpc_host.hpp: ldpc_encoder), OsdGen layout; host bytes only until a report is asked for
+    void *d_encgen = nullptr;             // its device copy: made by the first cwslg_fetch_decode_reports after a (re)load
+    bool enc_ready = false;               // columns 91..173 of the loaded H are invertible: words can be re-encoded
+    bool enc_dirty = false;               // enc_gen is newer than the device copy
 };
 
 struct SyncChannelBuffers {
@@ -131,7 +135,23 @@ inline void sync_free_shared(SyncShared &s)
     if (s.d_ft4c_win) (void)hipFree(s.d_ft4c_win);
     if (s.d_ldpc) (void)hipFree(s.d_ldpc);
     if (s.d_osdgen) (void)hipFree(s.d_osdgen);
+    if (s.d_encgen) (void)hipFree(s.d_encgen);
     s = SyncShared();
+}
+
+// The repository's fixed double-precision log10: the same bits on every machine.  x must be finite (a caller clamps).
+__device__ __forceinline__ double long_log10_fixed(double x)          // = orc_log10_fixed (oracle/sync_oracle.c)
+{
+    if (!(x > 0.0)) return -1.0e300;
+    int e = 0;
+    double m = x;
+    while (m >= 1.4142135623730951) { m = m * 0.5; ++e; }
+    while (m < 0.7071067811865476) { m = m * 2.0; --e; }
+    const double t = (m - 1.0) / (m + 1.0), t2 = t * t;
+    double s = 0.0;
+    for (int k = 21; k >= 1; k -= 2) s = s * t2 + 1.0 / (double)k;
+    const double ln_m = 2.0 * t * s;
+    return ((double)e * 0.6931471805599453 + ln_m) * 0.4342944819032518;
 }
 
 __device__ __forceinline__ float2 cmul_u(float2 a, float2 b)          // un-fused complex product

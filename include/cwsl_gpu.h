@@ -656,6 +656,54 @@ typedef struct {
 } cwslg_decode;          /* 40 bytes */
 int cwslg_fetch_decodes(cwslg_ctx *ctx, int group, uint64_t *start_epoch /* in/out */, cwslg_decode *dst, int max, int *n, int *n_total,
                         int *n_channels);
+/* FT8 signal reports (row a13; PARITY UNPINNED like the rest of the stage): per decode of cwslg_fetch_decodes an SNR figure and a tone check,
+ * made on the device from what is already there -- the channel's symbol-spectra plane (written by the boundary that made the list), the
+ * candidate's grid position and the loaded code.  A spot needs a report (cwslg_spot.snr_db); without this call a consumer of the device chain
+ * pulls each channel's 1.45 MB plane back and redoes the arithmetic on the host.  Structured like upstream ft8b's xsig / xnoi report, recalled and
+ * not copied, on the plane's own grid.  A FETCH like cwslg_fetch_decodes, not a stage: no record kind, no stamp, no launch at a boundary, no
+ * field in cwslg_stats, stats.sync_launches untouched.  tests/decode_reports_ref.py restates everything below in numpy.  Every operation is one
+ * un-fused float32 operation unless stated otherwise.
+ *   Re-encoder: cwslg_set_ldpc_code reduces H taking pivots in columns 91..173.  If those 83 columns are invertible the code is SYSTEMATIC:
+ *       the codeword of a 91-bit word is the word followed by the 83 parity bits H demands.  If they are not, the table is still loaded and
+ *       decodes as before; cwslg_fetch_decode_reports and cwslg_ft8_tones then return CWSLG_ERR_ARG with a text that says so.
+ *   Tones t[0..78] of a word: symbols 0..6, 36..42 and 72..78 are the Costas array 3,1,4,0,6,5,2; data symbol d (0..57) sits at n = d + 7
+ *       (d < 29) or d + 14 and its tone is graymap[4 cw[3d] + 2 cw[3d+1] + cw[3d+2]], graymap = 0,1,3,2,5,6,4,7 -- the inverse of what the soft
+ *       bits read.  cwslg_ft8_tones(ctx, bits[12], tones[79]) is this on its own, host work only, under the code in force.
+ *   For a decode with candidate (i = freq_bin, j = time_step) -- the list entry cwslg_decode.entry names:
+ *     Plane power: P[n][k] = S(i + 2 k, m), m = j + 12 + 4 n (n = 0..78, k = 0..7): the soft bits' addressing; +0 where m < 1, m > 372, the bin
+ *       is above 1920 or the bin is beyond the row.
+ *     Magnitude: s8 = sqrtf(P), correctly rounded.
+ *     nsync: of the 21 Costas symbols, the number whose FIRST maximum of s8 over k = 0..7 (ties to the lowest k) is at t[n].  By construction
+ *       this equals the entry's cwslg_ft8_soft.nsync.
+ *     nsymerr: of the 58 data symbols, the number whose first maximum of s8 is NOT at t[n]; 0..58.
+ *     xsig = sum of P[n][t[n]], xnoise = sum of P[n][(t[n] + 4) mod 7], both over n = 0..78 in the order a 64-lane wave evaluates them: lane l
+ *       holds term l, plus term l + 64 where that is below 79, added in that order (a[l] = term[l] + term[l + 64] for l < 15, term[l] otherwise);
+ *       then six halving steps a[l] = a[l] + a[l + h] for l < h, h = 32, 16, 8, 4, 2, 1; the result is a[0].
+ *     snr_db: r = xnoise > 0 ? xsig / xnoise - 1.0f : 0.0f;  x = r > 0.1f ? r : 0.001f;  x = min(x, FLT_MAX) (an infinite ratio, which no
+ *       logarithm is defined for, reports as the largest float's);  snr_db = max((float)(10.0 L((double)x) - 27.0), -24.0f), L the library's fixed
+ *       double-precision log10 (oracle/sync_oracle.c: orc_log10_fixed), so the bits are the same on every machine.  Upstream's baseline-referred
+ *       xsnr2 is not made.  How far this figure lies from an SNR in 2500 Hz is a measured property, not part of the contract.
+ * cwslg_fetch_decode_reports is cwslg_fetch_decodes' contract, points 1 to 7 above, with these differences: group must be CWSLG_GROUP_FT8 (FT4
+ * and every other group: CWSLG_ERR_ARG -- the FT4 chain keeps no symbol-aligned plane); dec receives byte-identical records to what
+ * cwslg_fetch_decodes returns for that epoch and max; rep[p] is the report of dec[p]; either output pointer may be null (nothing is written
+ * through it; the counts are the same).  Execution, one ticket and one serialised call of the group: the descriptors go up, the three harvest
+ * launches run, ONE further launch (a mode of decode_harvest_kernel, one wave per record) runs over the min(n_total, max) emitted records, ONE
+ * copy brings head, decodes and reports down, one synchronise.  The staging blocks are the group's, shared with cwslg_fetch_decodes and grown
+ * in the same way; the encoder's 2184-byte device copy is made by the first report call after a (re)load of the code: a context that never asks
+ * for reports holds no device byte of it.  It writes no record, list, stamp or statistic.
+ * The report uses the code IN FORCE AT THE CALL: words decoded under an earlier table are re-encoded under the new one (their first 91 bits are
+ * kept; parity, tones and therefore the figures are the new code's).
+ * Out of scope: unpacking to text, a-priori passes, signal subtraction, FT4 reports, xsnr2. */
+typedef struct {
+    float   snr_db;      /* see above; never below -24 */
+    float   xsig;        /* power at the re-encoded tones */
+    float   xnoise;      /* power at the tones (t + 4) mod 7 */
+    int16_t nsync;       /* Costas symbols whose strongest tone is the Costas tone, 0..21 */
+    int16_t nsymerr;     /* data symbols whose strongest tone is not the re-encoded one, 0..58 */
+} cwslg_decode_report;   /* 16 bytes */
+int cwslg_fetch_decode_reports(cwslg_ctx *ctx, int group, uint64_t *start_epoch /* in/out */, cwslg_decode *dec, cwslg_decode_report *rep, int max,
+                               int *n, int *n_total, int *n_channels);
+int cwslg_ft8_tones(cwslg_ctx *ctx, const uint8_t *bits /* [12] */, uint8_t *tones /* [79] */);
 int cwslg_fetch_slot(cwslg_ctx *ctx, int ch_id, int16_t *frame, size_t cap, void *list, size_t list_bytes,
                      cwslg_ft4_sync *ft4, int max_ft4, cwslg_slot_result *out);
 int cwslg_set_ft4_syncmin(cwslg_ctx *ctx, float syncmin);

@@ -25,6 +25,7 @@
 #include <stdexcept>
 #include <string>
 #include <vector>
+#include <array>
 #include <complex>
 
 #include "cwsl_gpu.h"
@@ -126,6 +127,28 @@ public:
         check(c_, rc);
         out.resize(n);
         return total;
+    }
+    // The same fetch with a signal report per decode (cwslg_fetch_decode_reports; FT8 group only): reports[p] belongs to out[p] -- snr_db for the
+    // spot, nsync / nsymerr to gate on.  Needs a systematic code loaded (cwslg_set_ldpc_code); the words are re-encoded under the code in force.
+    int fetchDecodeReports(int group, std::vector<cwslg_decode> &out, std::vector<cwslg_decode_report> &reports, std::uint64_t &startEpoch, int max = 4096,
+                           int *nChannels = nullptr)
+    {
+        out.resize(max > 0 ? max : 0);
+        reports.resize(out.size());
+        int n = 0, total = 0;
+        const int rc = cwslg_fetch_decode_reports(c_, group, &startEpoch, out.data(), reports.data(), static_cast<int>(out.size()), &n, &total, nChannels);
+        if (rc == CWSLG_ERR_NO_FRAME) { out.clear(); reports.clear(); return 0; }
+        check(c_, rc);
+        out.resize(n);
+        reports.resize(n);
+        return total;
+    }
+    // The 79 channel tones of a 91-bit word (cwslg_decode.bits) under the code in force: the reports' re-encoder on its own, host work only
+    std::array<std::uint8_t, 79> ft8Tones(const std::uint8_t *bits12)
+    {
+        std::array<std::uint8_t, 79> t{};
+        check(c_, cwslg_ft8_tones(c_, bits12, t.data()));
+        return t;
     }
     void synchronize() { check(c_, cwslg_synchronize(c_)); }
     // One block for each of several receivers in ONE call (cwslg_push_iq_many): for a host that serves thousands of streams, where a
