@@ -2104,7 +2104,14 @@ __global__ __launch_bounds__(256) void ft4_candidates_kernel(const SyncWork *__r
     const int nlen = (ib - ia + 1) / nseg, i0 = (ib - ia + 1) / 2;
     const double half = (double)(ib - ia + 1) / 2.0;
     const bool range_ok = (nfb - nfa) >= 20;
-    if (!range_ok) { if (tid == 0) *ncand_out = 0; return; }
+    // The parity planes are written on EVERY way out, as the restatement writes them: a search that ends early (a range too narrow, no baseline
+    // fit, a baseline that is not positive -- an all-zero frame, whose baseline is NaN) hands out savsm un-normalised and sbase as far as it
+    // got, never an earlier frame's values.  Every thread stores the entries it filled itself or ones filled before a barrier it has passed.
+    auto planes_out = [&]() {
+        CWSLG_GLOBAL float *red = as_global_rw(w->red), *red2 = as_global_rw(w->red2);
+        for (int i = tid; i < NB1; i += 256) { red[i] = s_savsm[i]; red2[i] = s_sbase[i]; }
+    };
+    if (!range_ok) { planes_out(); if (tid == 0) *ncand_out = 0; return; }
     for (int i = ia + tid; i <= ib; i += 256) s_sdb[i] = (float)(10.0 * log10_fixed((double)s_savg[i]));
     __syncthreads();
     // 10th percentile of each of the 10 segments (rank of every element inside its segment)
@@ -2169,7 +2176,7 @@ __global__ __launch_bounds__(256) void ft4_candidates_kernel(const SyncWork *__r
         s_ok = ok;
     }
     __syncthreads();
-    if (!s_ok) { if (tid == 0) *ncand_out = 0; return; }
+    if (!s_ok) { planes_out(); if (tid == 0) *ncand_out = 0; return; }
     int bad = 0;
     for (int i = ia + tid; i <= ib; i += 256) {
         const double u = (double)(i - i0) / half;
@@ -2178,13 +2185,10 @@ __global__ __launch_bounds__(256) void ft4_candidates_kernel(const SyncWork *__r
         s_sbase[i] = b;
         if (!(b > 0.0f)) bad = 1;
     }
-    if (__syncthreads_or(bad)) { if (tid == 0) *ncand_out = 0; return; }
+    if (__syncthreads_or(bad)) { planes_out(); if (tid == 0) *ncand_out = 0; return; }
     for (int i = nfa + tid; i <= nfb; i += 256) s_savsm[i] = s_savsm[i] / s_sbase[i];
     __syncthreads();
-    {
-        CWSLG_GLOBAL float *red = as_global_rw(w->red), *red2 = as_global_rw(w->red2);
-        for (int i = tid; i < NB1; i += 256) { red[i] = s_savsm[i]; red2[i] = s_sbase[i]; }   // for parity tests
-    }
+    planes_out();                                                       // for parity tests
     // local maxima, ascending bin, first maxcand kept
     constexpr int PER = 5;
     const float f_offset = -1.5f * 12000.0f / 576.0f;

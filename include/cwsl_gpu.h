@@ -711,7 +711,12 @@ int cwslg_set_ft4_syncmin(cwslg_ctx *ctx, float syncmin);
 /* Intermediate products of the sync stage for parity tests: what = 0 symbol spectra [372][nbins] float,
  * 1 red, 2 red2 (float[1921], before normalisation), 3 jpeak, 4 jpeak2 (int32[1921]).  *n_items = items available.
  * FT4 channels: 0 = [122][1168] windowed spectra, 1 = savsm/sbase (first 1153 entries), 2 = sbase,
- * 5 = frame spectrum (complex float[36289]), 6 = unit-power baseband of candidate 0 (complex float[4032]). */
+ * 5 = frame spectrum (complex float[36289]), 6 = unit-power baseband of candidate 0 (complex float[4032]).
+ * Planes 1 and 2 of an FT4 channel belong to the frame of the last boundary on EVERY outcome of the search.  Where the search ends before its
+ * local maxima -- a search range under 20 bins, fewer than 5 baseline points or a singular fit, a baseline that is not > 0 somewhere -- the list
+ * is empty, plane 1 is savsm NOT divided by the baseline and plane 2 the baseline as far as it was computed: +0 before the fit, the fitted
+ * values after it.  An all-zero frame ends that way: 10 log10(0) is -inf, the fit is NaN, plane 2 is NaN over the search range (a quiet NaN of
+ * unspecified sign and payload) and +0 outside it, plane 1 is +0. */
 int cwslg_sync_debug_fetch(cwslg_ctx *ctx, int ch_id, int what, void *dst, size_t cap_bytes, size_t *n_items, int *row_len);
 
 /* ---- candidate search of the 120 s modes (BASELINE.json configs[4]) ----
