@@ -212,7 +212,7 @@ ABI_SYMBOLS = [
     "cwslg_set_ldpc_code", "cwslg_enable_ft8_decode", "cwslg_fetch_ft8_decode", "cwslg_ldpc_decode",
     "cwslg_enable_ft8_osd", "cwslg_fetch_ft8_osd", "cwslg_osd_decode", "cwslg_enable_ft4_decode", "cwslg_fetch_ft4_decode",
     "cwslg_enable_ft4_osd", "cwslg_fetch_ft4_osd", "cwslg_fetch_decodes",
-    "cwslg_fetch_decode_reports", "cwslg_ft8_tones",
+    "cwslg_fetch_decode_reports", "cwslg_ft8_tones", "cwslg_fetch_ft4_decode_reports", "cwslg_ft4_tones",
     "cwslg_set_timing", "cwslg_demod_kernel_name", "cwslg_stream", "cwslg_channel_constants", "cwslg_phasor_checkpoint_stride", "cwslg_channel_phasor_checkpoints",
     "cwslg_slot_clock_next", "cwslg_pool_sizing", "cwslg_find_band", "cwslg_parse_decode_line",
     "cwslg_decoder_block_bytes", "cwslg_decoder_block_field", "cwslg_fill_decoder_block", "cwslg_decoder_route", "cwslg_decoder_command",
@@ -316,6 +316,8 @@ def load_library(build_if_missing=True):
     L.cwslg_fetch_decodes.argtypes = [vp, i32, C.POINTER(u64), vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     L.cwslg_fetch_decode_reports.argtypes = [vp, i32, C.POINTER(u64), vp, vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     L.cwslg_ft8_tones.argtypes = [vp, vp, vp]
+    L.cwslg_fetch_ft4_decode_reports.argtypes = [vp, C.POINTER(u64), vp, vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    L.cwslg_ft4_tones.argtypes = [vp, vp, vp]
     L.cwslg_sync_debug_fetch.argtypes = [vp, i32, i32, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(i32)]
     L.cwslg_get_stats.argtypes = [vp, C.POINTER(Stats)]
     L.cwslg_reset_stats.argtypes = [vp]
@@ -853,6 +855,29 @@ class Context:
             raise ValueError("bits: 12 bytes")
         tones = np.zeros(79, np.uint8)
         self._chk(self.L.cwslg_ft8_tones(self.h, b.ctypes.data, tones.ctypes.data))
+        return tones
+
+    def fetch_ft4_decode_reports(self, start_epoch=0, max=4096):
+        """cwslg_fetch_ft4_decode_reports: fetch_decodes("FT4") with a signal report per decode (needs a systematic code loaded).  -> None if no
+        channel takes part, else (records, reports, start_epoch, n_total, n_channels): reports a numpy array (DECODE_REPORT_DTYPE), reports[p] the
+        SNR figure (never below -21), xsig / xnoise and the nsync (0..16) / nsymerr (0..87) tone checks of records[p]."""
+        m = int(max)
+        dec, rep = np.zeros(m if m > 1 else 1, DECODE_DTYPE), np.zeros(m if m > 1 else 1, DECODE_REPORT_DTYPE)
+        t0, n, n_total, n_ch = C.c_uint64(int(start_epoch)), C.c_int(), C.c_int(), C.c_int()
+        rc = self.L.cwslg_fetch_ft4_decode_reports(self.h, C.byref(t0), dec.ctypes.data if m > 0 else None, rep.ctypes.data if m > 0 else None, m,
+                                                   C.byref(n), C.byref(n_total), C.byref(n_ch))
+        if rc == ERR_NO_FRAME:
+            return None
+        self._chk(rc)
+        return dec[:n.value].copy(), rep[:n.value].copy(), t0.value, n_total.value, n_ch.value
+
+    def ft4_tones(self, bits):
+        """cwslg_ft4_tones: the 103 FT4 channel tones of a 91-bit word (bits[12] as in a decode record; no rvec) under the code in force -> uint8[103]."""
+        b = np.ascontiguousarray(np.frombuffer(bytes(bits), np.uint8) if isinstance(bits, (bytes, bytearray)) else np.asarray(bits, np.uint8))
+        if b.shape != (12,):
+            raise ValueError("bits: 12 bytes")
+        tones = np.zeros(103, np.uint8)
+        self._chk(self.L.cwslg_ft4_tones(self.h, b.ctypes.data, tones.ctypes.data))
         return tones
 
     def enable_long_sync(self, on=True, nfa_hz=1400, nfb_hz=1600, minsync=1.2):

@@ -320,6 +320,7 @@ struct cwslg_ctx {
     LongConfig long_cfg;
     LongShared long_shared;
     HarvestStage harvest[2];           // cwslg_fetch_decodes: [0] the FT8 group's, [1] the FT4 group's
+    std::mutex report_mu;              // the report calls of BOTH groups, one at a time: they share the encoder's device copy (taken after harvest[].mu, before mu)
     // side stream: optionally (CWSLG_SYNC_VARIANT bit 3) carries the FT8 candidate kernel next to the following demod launch
     hipStream_t side = nullptr;
     hipEvent_t sync2d_done = nullptr, cand_done = nullptr, sync_tail = nullptr;

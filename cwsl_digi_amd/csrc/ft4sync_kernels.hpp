@@ -18,6 +18,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cmath>
+#include <vector>
 
 #include "sync_kernels.hpp"
 
@@ -45,6 +47,72 @@ struct alignas(16) Ft4Work {
     int *nrec;                                  // [max_cand]
     float2 *cd_dbg;                             // [4032] baseband of candidate 0 (tests)
 };
+
+// The tables of the coherent stage and of the soft-bit / report kernel as host arrays, built exactly as oracle/ft4sync_oracle.c builds its own
+// copy: the library uploads them once per context (sync_host.inc: ft4c_ensure_tables); tests/ft4_report_kernel_check.hip uploads the same.
+struct Ft4HostTables {
+    std::vector<float2> t;              // every float2 table, at the offsets below
+    std::vector<float> win;             // ft4_downsample's edge window, [630]
+    size_t o567 = 0, on2 = 0, o2n = 0, o64 = 0, o63 = 0, o4032 = 0, ocs = 0, otw = 0, o32 = 0;
+    Ft4Tables device(const float2 *b, const float *d_win) const { return Ft4Tables{b + o567, b + on2, b + o2n, b + o64, b + o63, b + o4032, b + ocs, b + otw, d_win}; }
+};
+inline Ft4HostTables ft4c_host_tables()
+{
+    Ft4HostTables H;
+    constexpr double pi = 3.14159265358979323846;
+    auto mk = [](double co, double si) { return make_float2((float)co, (float)si); };
+    std::vector<float2> &t = H.t;
+    const size_t o567 = 0, on2 = o567 + F4C_NA, o2n = on2 + F4C_N2, o64 = o2n + F4C_N2 + 1, o63 = o64 + 32, o4032 = o63 + 63,
+                 ocs = o4032 + F4C_NP, otw = ocs + 256, o32 = otw + 33 * 64, total = o32 + 32;
+    t.resize(total);
+    for (int k = 0; k < F4C_NA; ++k) t[o567 + k] = mk(std::cos(2.0 * pi * k / 567.0), -std::sin(2.0 * pi * k / 567.0));
+    for (int k = 0; k < F4C_N2; ++k) t[on2 + k] = mk(std::cos(2.0 * pi * k / 36288.0), -std::sin(2.0 * pi * k / 36288.0));
+    for (int k = 0; k <= F4C_N2; ++k) t[o2n + k] = mk(std::cos(2.0 * pi * k / 72576.0), -std::sin(2.0 * pi * k / 72576.0));
+    for (int k = 0; k < 32; ++k) t[o64 + k] = mk(std::cos(2.0 * pi * k / 64.0), -std::sin(2.0 * pi * k / 64.0));
+    for (int k = 0; k < 63; ++k) t[o63 + k] = mk(std::cos(2.0 * pi * k / 63.0), -std::sin(2.0 * pi * k / 63.0));
+    for (int k = 0; k < F4C_NP; ++k) t[o4032 + k] = mk(std::cos(2.0 * pi * k / 4032.0), -std::sin(2.0 * pi * k / 4032.0));
+    t[o567] = t[on2] = t[o2n] = t[o64] = t[o63] = t[o4032] = mk(1.0, 0.0);
+    t[o64 + 16] = mk(0.0, -1.0);
+    // the two twiddles between a DFT-by-columns and its 64-point row FFTs, W_N^(b c) with b < 64, are stored [c][b] (round 4): the kernels read them
+    // with b along the lanes -- one contiguous run per output row c instead of a cache line per lane (stride 8 c bytes in the flat table)
+    {
+        std::vector<float2> flat(t.begin() + on2, t.begin() + on2 + F4C_N2);
+        for (int cc = 0; cc < F4C_NA; ++cc) for (int b = 0; b < 64; ++b) t[on2 + (size_t)cc * 64 + b] = flat[(size_t)b * cc];
+        flat.assign(t.begin() + o4032, t.begin() + o4032 + F4C_NP);
+        for (int cc = 0; cc < 63; ++cc) for (int b = 0; b < 64; ++b) t[o4032 + (size_t)cc * 64 + b] = flat[(size_t)b * cc];
+    }
+    static const int icos4[4][4] = {{0, 1, 3, 2}, {1, 0, 2, 3}, {2, 3, 1, 0}, {3, 2, 0, 1}};
+    for (int b = 0; b < 4; ++b)
+        for (int sy = 0; sy < 4; ++sy)
+            for (int j = 0; j < 16; ++j) {
+                const int p = (2 * icos4[b][sy] * j) % 32;
+                float2 v = mk(std::cos(2.0 * pi * p / 32.0), std::sin(2.0 * pi * p / 32.0));
+                if (p == 0) v = mk(1.0, 0.0);
+                if (p == 8) v = mk(0.0, 1.0);
+                if (p == 16) v = mk(-1.0, 0.0);
+                if (p == 24) v = mk(0.0, -1.0);
+                t[ocs + 64 * b + 16 * sy + j] = v;
+            }
+    for (int d = -16; d <= 16; ++d)
+        for (int k = 0; k < 64; ++k) {
+            const double a = 2.0 * pi * (double)d * (double)(k + 1) * 36.0 / 12000.0;
+            t[otw + (d + 16) * 64 + k] = (d == 0) ? mk(1.0, 0.0) : mk(std::cos(a), std::sin(a));
+        }
+    // the soft-bit stage's symbol spectra (ft4soft_kernels.hpp): exp(+2 pi i p / 32), cardinal points exact as in csync
+    for (int p = 0; p < 32; ++p) t[o32 + p] = mk(std::cos(2.0 * pi * p / 32.0), std::sin(2.0 * pi * p / 32.0));
+    t[o32] = mk(1.0, 0.0); t[o32 + 8] = mk(0.0, 1.0); t[o32 + 16] = mk(-1.0, 0.0); t[o32 + 24] = mk(0.0, -1.0);
+    std::vector<float> &win = H.win;
+    win.resize(F4C_KHI - F4C_KLO + 1);
+    for (int k = F4C_KLO; k <= F4C_KHI; ++k) {
+        const int i = k + 126;
+        double wv = 1.0;
+        if (i < 63) wv = 0.5 * (1.0 + std::cos(pi * (double)(62 - i) / 63.0));
+        else if (i >= 567) wv = 0.5 * (1.0 + std::cos(pi * (double)(i - 567) / 63.0));
+        win[k - F4C_KLO] = (float)wv;
+    }
+    H.on2 = on2; H.o2n = o2n; H.o64 = o64; H.o63 = o63; H.o4032 = o4032; H.ocs = ocs; H.otw = otw; H.o32 = o32;
+    return H;
+}
 
 __device__ __forceinline__ float2 cmulc_f(float2 v, float2 w)         // v * conj(w), the restatement's CMULC
 {
@@ -280,8 +348,9 @@ struct F4BaseLds {
     const F4BaseLds L{s_y, s_cd, s_c1, s_w63, s_w64, s_part}
 
 // orc_ft4_downsample at f0: the 630 windowed bins around lroundf(f0 / df) -> inverse 4032 = 63 x 64 transform -> unit-mean-power baseband in
-// L.cd (four planes by sample index mod 4).  Called by all 256 threads of the workgroup; ends behind a barrier.
-__device__ __forceinline__ void f4_baseband(const F4BaseLds &L, const Ft4Work *w, const Ft4Tables &tb, float f0, int tid)
+// L.cd (four planes by sample index mod 4).  Called by all 256 threads of the workgroup; ends behind a barrier.  cx: the channel's frame spectrum
+// (Ft4Work::cx at a boundary; the FT4 decode reports of ft4soft_kernels.hpp hand in the same array from their own descriptor).
+__device__ __forceinline__ void f4_baseband(const F4BaseLds &L, const float2 *cx, const Ft4Tables &tb, float f0, int tid)
 {
     const int lane = tid & 63, wv = tid >> 6;
     const float df = 12000.0f / (float)F4C_NMAX;
@@ -296,7 +365,7 @@ __device__ __forceinline__ void f4_baseband(const F4BaseLds &L, const Ft4Work *w
         float2 v = make_float2(0.f, 0.f);
         const int idx = i0 + k;
         if (k >= F4C_KLO && k <= F4C_KHI && idx >= 0 && idx <= F4C_N2) {
-            const float2 x = gld2(w->cx + idx);
+            const float2 x = gld2(cx + idx);
             const float wk = tb.win[k - F4C_KLO];
             v = make_float2((x.x * wk) / 4032.0f, (x.y * wk) / 4032.0f);
         }
@@ -366,7 +435,7 @@ __global__ __launch_bounds__(256) void ft4_refine_kernel(const Ft4Work *__restri
     if (ncand > max_cand) ncand = max_cand;
     if (cand >= ncand) return;                      // workgroup-uniform
     const float f0 = as_global(w->cand)[cand].freq_hz;
-    f4_baseband(L, w, tb, f0, tid);
+    f4_baseband(L, w->cx, tb, f0, tid);
     if (cand == 0 && w->cd_dbg)
         for (int m = tid; m < F4C_NP; m += 256) gst2(w->cd_dbg + m, L.cd[m & 3][m >> 2]);
     // ---- the search of ft4_decode: 3 segments x (coarse, fine)

@@ -201,6 +201,21 @@ inline void ft8_tones_of(const uint32_t *cw, uint8_t *tones)
     }
 }
 
+// The 103 FT4 channel tones of a codeword (no rvec: descrambling stays with the consumer): Costas blocks 0132 1023 2310 3201 at symbols 0..3,
+// 33..36, 66..69, 99..102; data symbol d (0..86) at n = d + 4 (d < 29), d + 8 (d < 58) or d + 12, its tone graymap[2 cw[2d] + cw[2d+1]],
+// graymap = 0,1,3,2 -- the inverse of what ft4_softbits_kernel reads.
+inline void ft4_tones_of(const uint32_t *cw, uint8_t *tones)
+{
+    static const uint8_t icos4[16] = {0, 1, 3, 2, 1, 0, 2, 3, 2, 3, 1, 0, 3, 2, 0, 1}, graymap[4] = {0, 1, 3, 2};
+    for (int b = 0; b < 4; ++b)
+        for (int s = 0; s < 4; ++s) tones[33 * b + s] = icos4[4 * b + s];
+    for (int d = 0; d < 87; ++d) {
+        unsigned v = 0;
+        for (int b = 0; b < 2; ++b) v = (v << 1) | ((cw[(2 * d + b) >> 5] >> ((2 * d + b) & 31)) & 1u);
+        tones[d + (d < 29 ? 4 : d < 58 ? 8 : 12)] = graymap[v];
+    }
+}
+
 // d(c) of the contract: float32 adds of a[t] over the set bits of the error pattern, ascending t
 inline float osd_distance(const uint32_t *e, const float *a)
 {

@@ -59,63 +59,15 @@ int sync_ensure_shared(cwslg_ctx *c)
 int ft4c_ensure_tables(cwslg_ctx *c)
 {
     if (c->sync_shared.d_ft4c) return CWSLG_OK;
-    constexpr double pi = 3.14159265358979323846;
-    auto mk = [](double co, double si) { return make_float2((float)co, (float)si); };
-    std::vector<float2> t;
-    const size_t o567 = 0, on2 = o567 + F4C_NA, o2n = on2 + F4C_N2, o64 = o2n + F4C_N2 + 1, o63 = o64 + 32, o4032 = o63 + 63,
-                 ocs = o4032 + F4C_NP, otw = ocs + 256, o32 = otw + 33 * 64, total = o32 + 32;
-    t.resize(total);
-    for (int k = 0; k < F4C_NA; ++k) t[o567 + k] = mk(std::cos(2.0 * pi * k / 567.0), -std::sin(2.0 * pi * k / 567.0));
-    for (int k = 0; k < F4C_N2; ++k) t[on2 + k] = mk(std::cos(2.0 * pi * k / 36288.0), -std::sin(2.0 * pi * k / 36288.0));
-    for (int k = 0; k <= F4C_N2; ++k) t[o2n + k] = mk(std::cos(2.0 * pi * k / 72576.0), -std::sin(2.0 * pi * k / 72576.0));
-    for (int k = 0; k < 32; ++k) t[o64 + k] = mk(std::cos(2.0 * pi * k / 64.0), -std::sin(2.0 * pi * k / 64.0));
-    for (int k = 0; k < 63; ++k) t[o63 + k] = mk(std::cos(2.0 * pi * k / 63.0), -std::sin(2.0 * pi * k / 63.0));
-    for (int k = 0; k < F4C_NP; ++k) t[o4032 + k] = mk(std::cos(2.0 * pi * k / 4032.0), -std::sin(2.0 * pi * k / 4032.0));
-    t[o567] = t[on2] = t[o2n] = t[o64] = t[o63] = t[o4032] = mk(1.0, 0.0);
-    t[o64 + 16] = mk(0.0, -1.0);
-    // the two twiddles between a DFT-by-columns and its 64-point row FFTs, W_N^(b c) with b < 64, are stored [c][b] (round 4): the kernels read them
-    // with b along the lanes -- one contiguous run per output row c instead of a cache line per lane (stride 8 c bytes in the flat table)
-    {
-        std::vector<float2> flat(t.begin() + on2, t.begin() + on2 + F4C_N2);
-        for (int cc = 0; cc < F4C_NA; ++cc) for (int b = 0; b < 64; ++b) t[on2 + (size_t)cc * 64 + b] = flat[(size_t)b * cc];
-        flat.assign(t.begin() + o4032, t.begin() + o4032 + F4C_NP);
-        for (int cc = 0; cc < 63; ++cc) for (int b = 0; b < 64; ++b) t[o4032 + (size_t)cc * 64 + b] = flat[(size_t)b * cc];
-    }
-    static const int icos4[4][4] = {{0, 1, 3, 2}, {1, 0, 2, 3}, {2, 3, 1, 0}, {3, 2, 0, 1}};
-    for (int b = 0; b < 4; ++b)
-        for (int sy = 0; sy < 4; ++sy)
-            for (int j = 0; j < 16; ++j) {
-                const int p = (2 * icos4[b][sy] * j) % 32;
-                float2 v = mk(std::cos(2.0 * pi * p / 32.0), std::sin(2.0 * pi * p / 32.0));
-                if (p == 0) v = mk(1.0, 0.0);
-                if (p == 8) v = mk(0.0, 1.0);
-                if (p == 16) v = mk(-1.0, 0.0);
-                if (p == 24) v = mk(0.0, -1.0);
-                t[ocs + 64 * b + 16 * sy + j] = v;
-            }
-    for (int d = -16; d <= 16; ++d)
-        for (int k = 0; k < 64; ++k) {
-            const double a = 2.0 * pi * (double)d * (double)(k + 1) * 36.0 / 12000.0;
-            t[otw + (d + 16) * 64 + k] = (d == 0) ? mk(1.0, 0.0) : mk(std::cos(a), std::sin(a));
-        }
-    // the soft-bit stage's symbol spectra (ft4soft_kernels.hpp): exp(+2 pi i p / 32), cardinal points exact as in csync
-    for (int p = 0; p < 32; ++p) t[o32 + p] = mk(std::cos(2.0 * pi * p / 32.0), std::sin(2.0 * pi * p / 32.0));
-    t[o32] = mk(1.0, 0.0); t[o32 + 8] = mk(0.0, 1.0); t[o32 + 16] = mk(-1.0, 0.0); t[o32 + 24] = mk(0.0, -1.0);
-    std::vector<float> win(F4C_KHI - F4C_KLO + 1);
-    for (int k = F4C_KLO; k <= F4C_KHI; ++k) {
-        const int i = k + 126;
-        double wv = 1.0;
-        if (i < 63) wv = 0.5 * (1.0 + std::cos(pi * (double)(62 - i) / 63.0));
-        else if (i >= 567) wv = 0.5 * (1.0 + std::cos(pi * (double)(i - 567) / 63.0));
-        win[k - F4C_KLO] = (float)wv;
-    }
+    const Ft4HostTables ht = ft4c_host_tables();
+    const std::vector<float2> &t = ht.t;
+    const std::vector<float> &win = ht.win;
     HIPCHK(c, hipMalloc(&c->sync_shared.d_ft4c, t.size() * sizeof(float2)));
     HIPCHK(c, hipMemcpy(c->sync_shared.d_ft4c, t.data(), t.size() * sizeof(float2), hipMemcpyHostToDevice));
     HIPCHK(c, hipMalloc(&c->sync_shared.d_ft4c_win, win.size() * sizeof(float)));
     HIPCHK(c, hipMemcpy(c->sync_shared.d_ft4c_win, win.data(), win.size() * sizeof(float), hipMemcpyHostToDevice));
-    const float2 *b = c->sync_shared.d_ft4c;
-    c->ft4_tables = Ft4Tables{b + o567, b + on2, b + o2n, b + o64, b + o63, b + o4032, b + ocs, b + otw, c->sync_shared.d_ft4c_win};
-    c->sync_shared.ft4_w32 = b + o32;
+    c->ft4_tables = ht.device(c->sync_shared.d_ft4c, c->sync_shared.d_ft4c_win);
+    c->sync_shared.ft4_w32 = c->sync_shared.d_ft4c + ht.o32;
     return CWSLG_OK;
 }
 
@@ -490,8 +442,7 @@ int sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
             hipLaunchKernelGGL(ft4_refine_kernel, dim3((unsigned)cfg.max_cand, (unsigned)n4), dim3(256), 0, c->stream, f4, c->ft4_tables, cfg.max_cand);
             // soft bits: one workgroup per record slot behind the refinement; nrec and the candidate count are read on the device
             if (!a4.soft.empty())
-                hipLaunchKernelGGL(ft4_softbits_kernel, dim3(3u * (unsigned)cfg.max_cand, (unsigned)n4), dim3(256), 0, c->stream, f4, a4.d_soft, c->ft4_tables,
-                                   c->sync_shared.ft4_w32, cfg.max_cand);
+                ft4_softbits_launch(c->stream, f4, a4.d_soft, c->ft4_tables, c->sync_shared.ft4_w32, cfg.max_cand, (int)n4);
             // the decode: one wave per (record slot, metric set) behind the metrics it reads, the counts read on the device as the launch above
             // reads them; counted as a launch of its own, as the FT8 decode's is
             if (!a4.msg.empty()) {
@@ -970,8 +921,13 @@ int cwslg_fetch_ft4_osd(cwslg_ctx *c, int ch_id, cwslg_ft4_osd *dst, int max, in
 // under the context mutex, one ticket of the group, the work on a fetch stream behind the group's generation event with the mutex released --
 // except that what runs on the fetch stream is a descriptor upload, decode_harvest_kernel (count, scan, emit) and ONE copy down.  It writes only
 // the group's HarvestStage: no record, list, stamp or statistic changes.
-// reports (cwslg_fetch_decode_reports, FT8 only): a ReportDesc per channel goes up behind the HarvestDesc array in the same copy, ONE further
-// launch (report_launch) follows the three, and the reports come down behind the records in the same copy.
+// reports (cwslg_fetch_decode_reports for FT8, cwslg_fetch_ft4_decode_reports for FT4): a ReportDesc / Ft4ReportDesc per channel goes up behind
+// the HarvestDesc array in the same copy, ONE further launch (report_launch / ft4_report_launch) follows the three, and the reports come down
+// behind the records in the same copy.
+// FT4: a channel takes part only if its REC_MSG4 epoch is the frame's epoch, so sync_launch queued REC_MSG4 for that frame at the last boundary;
+// records_queued queues it only behind REC_SOFT4 and REC_FT4SYNC, i.e. with ft4_coherent on in the configuration of that boundary -- the same
+// switch under which sync_launch runs ft4_dft567 / ft4_fft64_unpack on the channel's Ft4Work (cx = d_cx).  d_cx therefore holds THAT frame's
+// spectrum, and the sync records read here are that boundary's too: no path hands a stale spectrum to the report.
 static int fetch_decodes_impl(cwslg_ctx *c, int group, uint64_t *start_epoch, cwslg_decode *dst, cwslg_decode_report *rep, int max, int *n, int *n_total,
                               int *n_channels, bool reports)
 {
@@ -981,8 +937,13 @@ static int fetch_decodes_impl(cwslg_ctx *c, int group, uint64_t *start_epoch, cw
     const int k_msg = ft4 ? REC_MSG4 : REC_MSG8, k_osd = ft4 ? REC_OSD4 : REC_OSD8;
     HarvestStage &hs = c->harvest[ft4 ? 1 : 0];
     std::lock_guard<std::mutex> serial(hs.mu);
+    std::unique_lock<std::mutex> report_serial;     // reports: also against the other group's report calls, from the encoder's upload to the synchronise
+    if (reports) report_serial = std::unique_lock<std::mutex>(c->report_mu);
     std::vector<HarvestDesc> descs;
     std::vector<ReportDesc> rdescs;
+    std::vector<Ft4ReportDesc> rdescs4;
+    Ft4Tables tb4{};
+    const float2 *d_w32 = nullptr;
     const uint32_t *d_enc = nullptr;
     size_t bound = 0;                   // no more decodes than entries
     ResultFetch rf;                     // ticket + lifetime, released when the copy is done or the call fails
@@ -1015,7 +976,15 @@ static int fetch_decodes_impl(cwslg_ctx *c, int group, uint64_t *start_epoch, cw
             d.ch_id = l.first;
             descs.push_back(d);
             bound += (size_t)d.cap * (ft4 ? 3 : 1);
-            if (reports) {
+            if (reports && ft4) {
+                Ft4ReportDesc r{};
+                r.cx = b.d_cx;
+                r.rec = (const Ft4Rec *)b.d_rec;
+                r.nrec = b.d_nrec;
+                r.cnt = b.d_ncand;
+                r.cap = d.cap;
+                rdescs4.push_back(r);
+            } else if (reports) {
                 ReportDesc r{};
                 r.spectra = b.d_spectra;
                 r.list = b.d_cand;
@@ -1026,8 +995,8 @@ static int fetch_decodes_impl(cwslg_ctx *c, int group, uint64_t *start_epoch, cw
         if (descs.empty()) return CWSLG_ERR_NO_FRAME;
         hipSetDevice(c->device);
         if (reports) {
-            // the encoder's device copy, made by the first call after a (re)load.  The report launches are its only readers; they belong to this
-            // group's calls, which hs.mu serialises and which synchronise before they return: none is in flight now
+            // the encoder's device copy, made by the first call after a (re)load.  The report launches of the two groups are its only readers; they
+            // belong to calls that report_mu serialises and that synchronise before they return: none is in flight now
             SyncShared &s = c->sync_shared;
             if (!s.d_encgen) HIPCHK(c, hipMalloc(&s.d_encgen, sizeof(OsdGen)));
             if (s.enc_dirty) {
@@ -1035,6 +1004,8 @@ static int fetch_decodes_impl(cwslg_ctx *c, int group, uint64_t *start_epoch, cw
                 s.enc_dirty = false;
             }
             d_enc = (const uint32_t *)s.d_encgen;
+            tb4 = c->ft4_tables;            // (FT4: built by the boundary that made the records)
+            d_w32 = s.ft4_w32;
         }
         *start_epoch = E;
         const int rc = begin_result_fetch(c, c->chans[descs[0].ch_id], rf);
@@ -1043,7 +1014,8 @@ static int fetch_decodes_impl(cwslg_ctx *c, int group, uint64_t *start_epoch, cw
     // no context lock from here on
     const size_t nch = descs.size(), lim = std::min((size_t)std::max(max, 0), bound);
     auto pad = [](size_t v) { return (v + 255) & ~size_t(255); };
-    const size_t desc_bytes = nch * sizeof(HarvestDesc), rdesc_bytes = rdescs.size() * sizeof(ReportDesc), cnt_bytes = pad(nch * sizeof(unsigned));
+    const size_t desc_bytes = nch * sizeof(HarvestDesc), cnt_bytes = pad(nch * sizeof(unsigned));
+    const size_t rdesc_bytes = ft4 ? rdescs4.size() * sizeof(Ft4ReportDesc) : rdescs.size() * sizeof(ReportDesc);
     const size_t up_bytes = reports ? pad(desc_bytes) + rdesc_bytes : desc_bytes, up_pad = pad(up_bytes);
     // down: head | lim records | (reports: from the next 16-byte boundary) lim reports
     const size_t rec_words = HARVEST_HEAD_WORDS + lim * HARVEST_REC_WORDS, rep_at = (rec_words + 3) & ~size_t(3);
@@ -1062,7 +1034,7 @@ static int fetch_decodes_impl(cwslg_ctx *c, int group, uint64_t *start_epoch, cw
         hs.d_bytes = pad(d_need + d_need / 2);
     }
     std::memcpy(hs.h, descs.data(), desc_bytes);
-    if (reports) std::memcpy(hs.h + pad(desc_bytes), rdescs.data(), rdesc_bytes);
+    if (reports) std::memcpy(hs.h + pad(desc_bytes), ft4 ? (const void *)rdescs4.data() : (const void *)rdescs.data(), rdesc_bytes);
     unsigned *h_out = (unsigned *)(hs.h + up_pad);
     const HarvestDesc *d_desc = (const HarvestDesc *)hs.d;
     unsigned *d_counts = (unsigned *)(hs.d + up_pad), *d_offsets = (unsigned *)(hs.d + up_pad + cnt_bytes);
@@ -1070,7 +1042,10 @@ static int fetch_decodes_impl(cwslg_ctx *c, int group, uint64_t *start_epoch, cw
     HIPCHK(c, hipStreamWaitEvent(rf.fs, rf.ev, 0));
     HIPCHK(c, hipMemcpyAsync(hs.d, hs.h, up_bytes, hipMemcpyHostToDevice, rf.fs));
     harvest_launch(rf.fs, d_desc, d_counts, d_offsets, d_out, (int)nch, (int)lim, ft4 ? 1 : 0);
-    if (reports) report_launch(rf.fs, (const ReportDesc *)(hs.d + pad(desc_bytes)), d_offsets, d_out, d_enc, d_out + rep_at, (int)nch, (int)lim);
+    if (reports && ft4)
+        ft4_report_launch(rf.fs, (const Ft4ReportDesc *)(hs.d + pad(desc_bytes)), d_offsets, d_out, d_enc, d_out + rep_at, tb4, d_w32, (int)nch, (int)lim);
+    else if (reports)
+        report_launch(rf.fs, (const ReportDesc *)(hs.d + pad(desc_bytes)), d_offsets, d_out, d_enc, d_out + rep_at, (int)nch, (int)lim);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(h_out, d_out, out_bytes, hipMemcpyDeviceToHost, rf.fs));
     HIPCHK(c, hipStreamSynchronize(rf.fs));
@@ -1105,8 +1080,19 @@ int cwslg_fetch_decode_reports(cwslg_ctx *c, int group, uint64_t *start_epoch, c
     return fetch_decodes_impl(c, group, start_epoch, dec, rep, max, n, n_total, n_channels, true);
 }
 
-// The 79 channel tones of a 91-bit word under the code in force: the re-encoder of the reports on its own, host work only.
-int cwslg_ft8_tones(cwslg_ctx *c, const uint8_t *bits, uint8_t *tones)
+// The FT4 group's call (ft4soft_kernels.hpp: FT4S_REPORT; the contract is the header's, "FT4 signal reports").
+int cwslg_fetch_ft4_decode_reports(cwslg_ctx *c, uint64_t *start_epoch, cwslg_decode *dec, cwslg_decode_report *rep, int max, int *n, int *n_total,
+                                   int *n_channels)
+{
+    if (n) *n = 0;
+    if (n_total) *n_total = 0;
+    if (n_channels) *n_channels = 0;
+    if (!c || !start_epoch || !n || !n_total) return CWSLG_ERR_ARG;
+    return fetch_decodes_impl(c, CWSLG_GROUP_FT4, start_epoch, dec, rep, max, n, n_total, n_channels, true);
+}
+
+// The channel tones of a 91-bit word under the code in force: the re-encoder of the reports on its own, host work only.
+static int tones_impl(cwslg_ctx *c, const uint8_t *bits, uint8_t *tones, bool ft4)
 {
     if (!c || !bits || !tones) return CWSLG_ERR_ARG;
     std::lock_guard<std::mutex> g(c->mu);
@@ -1117,9 +1103,11 @@ int cwslg_ft8_tones(cwslg_ctx *c, const uint8_t *bits, uint8_t *tones)
     std::memcpy(&enc, c->sync_shared.enc_gen, sizeof(OsdGen));
     uint32_t cw[OSD_GW];
     ldpc_encode(enc, bits, cw);
-    ft8_tones_of(cw, tones);
+    if (ft4) ft4_tones_of(cw, tones); else ft8_tones_of(cw, tones);
     return CWSLG_OK;
 }
+int cwslg_ft8_tones(cwslg_ctx *c, const uint8_t *bits, uint8_t *tones) { return tones_impl(c, bits, tones, false); }
+int cwslg_ft4_tones(cwslg_ctx *c, const uint8_t *bits, uint8_t *tones) { return tones_impl(c, bits, tones, true); }
 
 int cwslg_sync_debug_fetch(cwslg_ctx *c, int ch_id, int what, void *dst, size_t cap_bytes, size_t *n_items, int *row_len)
 {

@@ -79,7 +79,7 @@ struct SyncShared {
     bool osd_ready = false;               // the loaded code has rank 83: OSD may be enabled
     bool osd_dirty = false;               // osd_gen is newer than the device copy
     uint32_t enc_gen[91 * 6] = {};        // the systematic encoder of the loaded code (ldpc_host.hpp: ldpc_encoder), OsdGen layout; host bytes only until a report is asked for
-    void *d_encgen = nullptr;             // its device copy: made by the first cwslg_fetch_decode_reports after a (re)load
+    void *d_encgen = nullptr;             // its device copy: made by the first cwslg_fetch_decode_reports / cwslg_fetch_ft4_decode_reports after a (re)load
     bool enc_ready = false;               // columns 91..173 of the loaded H are invertible: words can be re-encoded
     bool enc_dirty = false;               // enc_gen is newer than the device copy
 };

@@ -684,7 +684,7 @@ int cwslg_fetch_decodes(cwslg_ctx *ctx, int group, uint64_t *start_epoch /* in/o
  *       double-precision log10 (oracle/sync_oracle.c: orc_log10_fixed), so the bits are the same on every machine.  Upstream's baseline-referred
  *       xsnr2 is not made.  How far this figure lies from an SNR in 2500 Hz is a measured property, not part of the contract.
  * cwslg_fetch_decode_reports is cwslg_fetch_decodes' contract, points 1 to 7 above, with these differences: group must be CWSLG_GROUP_FT8 (FT4
- * and every other group: CWSLG_ERR_ARG -- the FT4 chain keeps no symbol-aligned plane); dec receives byte-identical records to what
+ * and every other group: CWSLG_ERR_ARG -- the FT4 chain keeps no symbol-aligned plane; its reports are cwslg_fetch_ft4_decode_reports below); dec receives byte-identical records to what
  * cwslg_fetch_decodes returns for that epoch and max; rep[p] is the report of dec[p]; either output pointer may be null (nothing is written
  * through it; the counts are the same).  Execution, one ticket and one serialised call of the group: the descriptors go up, the three harvest
  * launches run, ONE further launch (a mode of decode_harvest_kernel, one wave per record) runs over the min(n_total, max) emitted records, ONE
@@ -693,17 +693,57 @@ int cwslg_fetch_decodes(cwslg_ctx *ctx, int group, uint64_t *start_epoch /* in/o
  * for reports holds no device byte of it.  It writes no record, list, stamp or statistic.
  * The report uses the code IN FORCE AT THE CALL: words decoded under an earlier table are re-encoded under the new one (their first 91 bits are
  * kept; parity, tones and therefore the figures are the new code's).
- * Out of scope: unpacking to text, a-priori passes, signal subtraction, FT4 reports, xsnr2. */
+ * Out of scope: unpacking to text, a-priori passes, signal subtraction, xsnr2 (FT4 reports: the next block). */
 typedef struct {
-    float   snr_db;      /* see above; never below -24 */
+    float   snr_db;      /* see above; never below -24 (FT4: -21) */
     float   xsig;        /* power at the re-encoded tones */
-    float   xnoise;      /* power at the tones (t + 4) mod 7 */
-    int16_t nsync;       /* Costas symbols whose strongest tone is the Costas tone, 0..21 */
-    int16_t nsymerr;     /* data symbols whose strongest tone is not the re-encoded one, 0..58 */
+    float   xnoise;      /* power at the tones (t + 4) mod 7 (FT4: (t + 2) & 3) */
+    int16_t nsync;       /* Costas symbols whose strongest tone is the Costas tone, 0..21 (FT4: 0..16) */
+    int16_t nsymerr;     /* data symbols whose strongest tone is not the re-encoded one, 0..58 (FT4: 0..87) */
 } cwslg_decode_report;   /* 16 bytes */
 int cwslg_fetch_decode_reports(cwslg_ctx *ctx, int group, uint64_t *start_epoch /* in/out */, cwslg_decode *dec, cwslg_decode_report *rep, int max,
                                int *n, int *n_total, int *n_channels);
 int cwslg_ft8_tones(cwslg_ctx *ctx, const uint8_t *bits /* [12] */, uint8_t *tones /* [79] */);
+/* FT4 signal reports (row a13; PARITY UNPINNED like the rest of the stage): the same 16-byte cwslg_decode_report beside every decode of
+ * cwslg_fetch_decodes(CWSLG_GROUP_FT4), made on the device from what is there when the fetch is made -- the channel's frame spectrum (written by
+ * the boundary that made the records), the sync record's refined frequency and start, and the loaded code.  Without this call a consumer pulls
+ * the channel's 290 KB frame spectrum back and redoes the downsample and 412 symbol transforms per decode on the host.  A FETCH, not a stage:
+ * no record kind, no stamp, no launch at a boundary, no field in cwslg_stats, stats.sync_launches untouched.  tests/ft4_decode_reports_ref.py
+ * restates everything below in numpy.  Every operation is one un-fused float32 operation unless written as fmaf.
+ *   Tones t[0..102] of a word: the codeword is the FT8 report's systematic re-encoding of the 91 bits (above; the same errors for a table whose
+ *       columns 91..173 are singular).  No rvec: descrambling stays with the consumer, as everywhere in the FT4 chain.  Symbols 0..3, 33..36,
+ *       66..69 and 99..102 carry the Costas blocks 0132, 1023, 2310, 3201; data symbol d (0..86) sits at n = d + 4 (d < 29), d + 8 (d < 58) or
+ *       d + 12 and its tone is graymap[2 cw[2d] + cw[2d+1]], graymap = 0,1,3,2 -- the inverse of what the soft bits read.
+ *       cwslg_ft4_tones(ctx, bits[12], tones[103]) is this on its own, host work only, under the code in force.
+ *   For a decode whose entry names the sync record (f1_hz, ibest) -- cwslg_fetch_ft4_sync's compacted order:
+ *     Spectra: the baseband is the soft bits' (orc_ft4_downsample at f1_hz); cs[n][q] (n = 0..102, q = 0..3) is cwslg_ft4_soft's 32-term fmaf
+ *       chain over the samples ibest + 32 n .. + 31, +0 outside 0..4031: the SAME bits as the soft-bit stage computes (one device text).
+ *     Power: P[n][q] = fmaf(re, re, im * im).  Magnitude: sqrtf(P), correctly rounded.
+ *     nsync: of the 16 Costas symbols, the number whose FIRST maximum of the magnitude over q = 0..3 (ties to the lowest q) is t[n]; 0..16.  By
+ *       construction this equals the record's cwslg_ft4_soft.nsync.  On an all-zero baseband it is 4: tone 0 wins every tie and each Costas
+ *       block contains one 0.
+ *     nsymerr: of the 87 data symbols, the number whose first maximum is NOT t[n]; 0..87.
+ *     xsig = sum of P[n][t[n]], xnoise = sum of P[n][(t[n] + 2) & 3] (the tone two bins away is orthogonal over the 32-sample symbol), both over
+ *       n = 0..102 in the order a 64-lane wave evaluates them: a[l] = term[l] + term[l + 64] for l < 39, term[l] otherwise; then six halving
+ *       steps a[l] = a[l] + a[l + h] for l < h, h = 32, 16, 8, 4, 2, 1; the result is a[0].
+ *     snr_db: r = xnoise > 0 ? xsig / xnoise - 1.0f : 0.0f;  x = r > 0.1f ? r : 0.001f;  x = min(x, FLT_MAX);
+ *       snr_db = max((float)(10.0 L((double)x) - 20.8), -21.0f), L the fixed log10 of the FT8 report.  20.8 is 10 log10(2500 / 20.8333), the
+ *       ratio of the reference bandwidth to a tone bin's noise bandwidth; it contains no fitted term.  -21 is the floor FT4 reports
+ *       conventionally have; it is reached at r = 0.955, so the 0.1 / 0.001 branch never shows in snr_db.  A NaN xsig or xnoise fails both
+ *       comparisons and reports -21: the logarithm never sees NaN or infinity.  How far the figure lies from an SNR in 2500 Hz is a measured
+ *       property, not part of the contract.
+ * cwslg_fetch_ft4_decode_reports is cwslg_fetch_decodes' contract for CWSLG_GROUP_FT4, points 1 to 7 above, with these additions: dec receives
+ * byte-identical records to what cwslg_fetch_decodes returns for that epoch and max; rep[p] is the report of dec[p] (nsync 0..16, nsymerr 0..87);
+ * either output pointer may be null.  Execution, one ticket and one serialised call of the group: the descriptors go up (a second per-channel
+ * descriptor with the spectrum, the sync records, nrec and the capacity rides in the same copy), the three harvest launches run, ONE further
+ * launch (a wave-uniform mode of ft4_softbits_kernel, one 256-thread workgroup per record, the grid sized by max) runs over the
+ * min(n_total, max) emitted records, ONE copy brings head, decodes and reports down, one synchronise.  Staging and the encoder's device copy are
+ * as for the FT8 call; the code IN FORCE AT THE CALL is used.  A channel takes part only if its decode records are of the frame's epoch, which
+ * implies that the last boundary ran the coherent stage on it: the spectrum read is that frame's.
+ * Out of scope: unpacking to text, rvec, a-priori passes, signal subtraction, a baseline-referred SNR. */
+int cwslg_fetch_ft4_decode_reports(cwslg_ctx *ctx, uint64_t *start_epoch /* in/out */, cwslg_decode *dec, cwslg_decode_report *rep, int max,
+                                   int *n, int *n_total, int *n_channels);
+int cwslg_ft4_tones(cwslg_ctx *ctx, const uint8_t *bits /* [12] */, uint8_t *tones /* [103] */);
 int cwslg_fetch_slot(cwslg_ctx *ctx, int ch_id, int16_t *frame, size_t cap, void *list, size_t list_bytes,
                      cwslg_ft4_sync *ft4, int max_ft4, cwslg_slot_result *out);
 int cwslg_set_ft4_syncmin(cwslg_ctx *ctx, float syncmin);

@@ -150,6 +150,28 @@ public:
         check(c_, cwslg_ft8_tones(c_, bits12, t.data()));
         return t;
     }
+    // The FT4 group's fetch with a signal report per decode (cwslg_fetch_ft4_decode_reports): reports[p] belongs to out[p]; nsync is 0..16, nsymerr
+    // 0..87, snr_db never below -21.  Needs a systematic code loaded; the words are re-encoded under the code in force (no rvec).
+    int fetchFt4DecodeReports(std::vector<cwslg_decode> &out, std::vector<cwslg_decode_report> &reports, std::uint64_t &startEpoch, int max = 4096,
+                              int *nChannels = nullptr)
+    {
+        out.resize(max > 0 ? max : 0);
+        reports.resize(out.size());
+        int n = 0, total = 0;
+        const int rc = cwslg_fetch_ft4_decode_reports(c_, &startEpoch, out.data(), reports.data(), static_cast<int>(out.size()), &n, &total, nChannels);
+        if (rc == CWSLG_ERR_NO_FRAME) { out.clear(); reports.clear(); return 0; }
+        check(c_, rc);
+        out.resize(n);
+        reports.resize(n);
+        return total;
+    }
+    // The 103 FT4 channel tones of a 91-bit word (cwslg_decode.bits) under the code in force: host work only
+    std::array<std::uint8_t, 103> ft4Tones(const std::uint8_t *bits12)
+    {
+        std::array<std::uint8_t, 103> t{};
+        check(c_, cwslg_ft4_tones(c_, bits12, t.data()));
+        return t;
+    }
     void synchronize() { check(c_, cwslg_synchronize(c_)); }
     // One block for each of several receivers in ONE call (cwslg_push_iq_many): for a host that serves thousands of streams, where a
     // per-receiver push per block (Receiver.hpp:242-249, ReceiverPort::push below) would mean hundreds of thousands of copies a second.
