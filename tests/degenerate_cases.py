@@ -25,6 +25,7 @@ import numpy as np
 import decode_reports_ref as RR
 import decodes_ref as DR
 import ft4_decode_cases as D
+import ft4_decode_reports_ref as RR4
 import ft4_osd_cases as X
 import ft4_softbits_ref as R4
 import ft8_softbits_ref as R8
@@ -263,6 +264,18 @@ def reports_of(planes, lists, dec):
     return RR.reports(K.encoder(SEED), planes, lists, dec)
 
 
+def reports4_of(spectra, records, dec):
+    """ft4_decode_reports_ref.reports under the seed code: spectra[ch_id] the frame spectrum (ft4_cx), records[ch_id] the sync records."""
+    from oracle import oracle as orc
+    return RR4.reports(orc, K.encoder(SEED), spectra, records, dec)
+
+
+def ft4_reports(ref, osd=True):
+    """(decodes, reports) of ONE FT4 channel (ch_id 0) from a reference() result: what cwslg_fetch_ft4_decode_reports hands out for it."""
+    dec, _ = DR.decodes("FT4", [decodes_of("FT4", 0, ref, osd)])
+    return dec, reports4_of({0: ref["cx"]}, {0: ref["recs"]}, dec)
+
+
 # ---- the conditions -------------------------------------------------------------------------------------------------------------------------------------
 def bits12(mode, tx):
     """bits[12] of a record that carries the message of transmission tx."""
@@ -325,10 +338,15 @@ def assert_decoded(mode, ref, tx):
     return hit
 
 
-def assert_conditions(name, mode, cfg, ref):
+def assert_conditions(name, mode, cfg, ref, fast_frame=False):
     """What recipe `name` must put before the kernels, on the channel of `mode` under configuration `cfg`.  The floors sit well under what the
     restatements give on the oracle's frames (tests/test_degenerate_inputs.py lists them); the frames are deterministic: a floor that fails means
-    the recipe changes, not the floor."""
+    the recipe changes, not the floor.  fast_frame: `ref` was made of a fast-mode frame, which may differ from the oracle's by 1 LSB per sample;
+    ONE condition is then not asserted -- blocker8's "max |llr| above 1000": that maximum belongs to ONE junk candidate beside the blocker (9332 on the
+    oracle's frame, the next candidate's maximum is 13.3) and single LSBs of the frame decide it: the oracle's frame with a random -1, 0 or +1 on
+    every sample gives 13.3, 6599 or 4666 (three draws), the fast mode's frame gave 13.3 on an MI355X (tests/test_gpu_degenerate_frames.py
+    prints it).  The LLRs themselves are still compared on bits with the restatement of that frame, and every
+    other condition holds in both modes."""
     fr, lst = ref["frame"], ref["list"]
     is_open = cfg.name == "open"
     if (name, mode) in ZERO_FRAMES:
@@ -364,7 +382,7 @@ def assert_conditions(name, mode, cfg, ref):
     elif name in ("cut4_tail", "cut4_head") and mode == "FT4":
         assert exact_zero_llrs(ref["llr"]) >= 30 and segments(ref["recs"]) == {1, 2, 3}
     elif name == "blocker8" and mode == "FT8":
-        assert np.abs(ref["llr"]).max() > 1000
+        assert fast_frame or np.abs(ref["llr"]).max() > 1000
         assert_decoded("FT8", ref, WEAK8)
     elif name == "blocker4" and mode == "FT4":
         assert_decoded("FT4", ref, WEAK4)

@@ -3,7 +3,9 @@ each, transmissions that carry codewords of the first seed code of tests/ldpc_ca
 must hand out for a channel, an epoch and the configuration in force at that epoch's boundary, computed on the CPU alone from the restatements
 (oracle.Channel -> oracle.ft8_sync / ft4_candidates -> oracle.ft4_sync_all -> ft8_softbits_ref / ft4_softbits_ref -> ldpc_ref -> osd_ref), as
 byte strings in the layout of the C records.  tests/test_record_race_inputs.py vets the slots: any two epochs differ in every stage, so a stale
-or a mixed generation is always visible.  If a property is missing there the amplitudes below change, not the assertions."""
+or a mixed generation is always visible.  If a property is missing there the amplitudes below change, not the assertions.
+group_expected() does the same for the group fetches of tests/test_gpu_report_fetch_races.py: the decodes and the signal reports of a whole
+group and epoch (decodes_ref, decode_reports_ref, ft4_decode_reports_ref on the same CPU chain)."""
 import collections
 import functools
 
@@ -229,3 +231,50 @@ def expected(mode, k, e, cfg=ALL_ON):
     out["osd"] = c["osd"].tobytes() if soft and cfg.decode and cfg.osd else None
     assert set(out) == set(STAGES[mode])
     return out
+
+
+# ---- the group fetches ------------------------------------------------------------------------------------------------------------------------------
+def chain_runs(mode, cfg):
+    """The whole chain up to the decode ran at a boundary under cfg: only then do the group fetches hand anything out under that epoch."""
+    return bool(cfg.soft and cfg.decode and (mode == "FT8" or cfg.coherent))
+
+
+@functools.lru_cache(maxsize=None)
+def _group(mode, e, max_cand, osd):
+    """(decodes, reports) of epoch e with the channel INDEX in ch_id; read-only."""
+    from oracle import oracle as orc
+    import decode_reports_ref as RR8
+    import decodes_ref as DR
+    import ft4_decode_reports_ref as RR4
+    import report_kernel_cases as K
+    chains = [chain(mode, k, e, max_cand) for k in range(len(RF[mode]))]
+    inp = [(k, DR.where_ft8(c["list"]) if mode == "FT8" else DR.where_ft4(c["sync"]), c["msg"], c["osd"] if osd else None) for k, c in enumerate(chains)]
+    dec, n_total = DR.decodes(mode, inp)
+    assert n_total == len(dec)
+    enc = K.encoder(SEED)
+    if mode == "FT8":
+        planes = {k: np.ascontiguousarray(orc.ft8_spectra(c["frame"], S8.soft_pitch(SYNC["f_hi"])), np.float32) for k, c in enumerate(chains)}
+        rep = RR8.reports(enc, planes, {k: c["list"] for k, c in enumerate(chains)}, dec)
+    else:
+        rep = RR4.reports(orc, enc, {k: orc.ft4_bigspec(c["frame"]) for k, c in enumerate(chains)}, {k: c["sync"] for k, c in enumerate(chains)}, dec)
+    dec.setflags(write=False)
+    rep.setflags(write=False)
+    return dec, rep
+
+
+def group_expected(mode, e, cfg, ch_ids):
+    """What cwslg_fetch_decodes and the mode's report fetch hand out for the whole group under start_epoch(mode, e) when `cfg` was in force at
+    that epoch's boundary, computed on the CPU alone: (decodes DECODE_DTYPE[n_total], reports REPORT_DTYPE[n_total], n_total) -- decodes_ref on
+    chain() of every channel (OSD records only if cfg.osd), decode_reports_ref on the oracle's symbol-spectra planes and the lists (FT8),
+    ft4_decode_reports_ref on the oracle's frame spectra and the sync records (FT4), under the encoder of the seed code.  ch_ids: the library's
+    channel ids in the order of RF[mode], ascending.  None where the chain did not run at that boundary: the group fetches then hand out nothing
+    stamped with that epoch.  A caller that asked with `max` compares against the first min(n_total, max) of both."""
+    if not chain_runs(mode, cfg):
+        return None
+    ch_ids = [int(c) for c in ch_ids]
+    assert len(ch_ids) == len(RF[mode]) and ch_ids == sorted(ch_ids), ch_ids
+    dec, rep = _group(mode, e, cfg.max_cand, bool(cfg.osd))
+    dec = dec.copy()
+    dec["ch_id"] = np.asarray(ch_ids, np.int32)[dec["ch_id"]]
+    dec.setflags(write=False)
+    return dec, rep, len(dec)

@@ -15,6 +15,9 @@ calls again on the library's output):
   cut8_*              5000 exact-zero LLRs or more;   cut4_*: 30 or more, records in all three segments;
   blocker8 / blocker4 the weak message is decoded; FT8: max |llr| above 1000;
   comb, FT4, open     100 records or more, 50 all-zero words or more, none of them among decodes_ref's decodes.
+  FT4 reports         (test_ft4_reports_of_the_recipes) clean4 and blocker4 one decode each with nsync 16 and nsymerr 0, 16.0 dB and above 8 dB;
+                      cut4_tail 7 decodes, 2 of them by OSD alone, 5 on records with ibest < 0, nsymerr 22..27, nsync 9 or 10; cut4_head one
+                      OSD-only decode with nsymerr 29; no FT4 decode anywhere else; every xsig and xnoise finite and positive.
 A recipe that misses its condition is changed, never the condition.
 
 No NaN and no infinity in any restatement's output -- with ONE exception, found while this module was written and pinned here: the baseline
@@ -74,6 +77,41 @@ def test_ordinary_slot(oracle, cfg):
         ref = G.reference(oracle, mode, G.ordinary_frame(mode), cfg)
         G.assert_ordinary(mode, ref, tones)
         assert all(np.isfinite(a).all() for a in G.stage_floats(ref).values())
+
+
+# ---- what the recipes give the FT4 report ----------------------------------------------------------------------------------------------------------
+FT4_DECODING = ("clean4", "blocker4", "cut4_tail", "cut4_head")
+
+
+@pytest.mark.parametrize("cfg", [G.UPSTREAM, G.OPEN], ids=lambda c: c.name)
+def test_ft4_reports_of_the_recipes(oracle, cfg):
+    """cwslg_fetch_ft4_decode_reports meets, through the library, exactly the decodes its kernel has not met elsewhere: records with ibest < 0
+    (leading symbols exact zeros, which tie to tone 0), OSD-only words, noise-free transmissions.  Measured with the restatements, identical
+    under both configurations; the reports cost under 0.1 s per recipe."""
+    got = {}
+    for name in G.RECIPES:
+        ref = _ref(oracle, name, "FT4", cfg)
+        dec, rep = G.ft4_reports(ref)
+        assert len(rep) == len(dec) and np.isfinite(rep["xsig"]).all() and np.isfinite(rep["xnoise"]).all() and np.isfinite(rep["snr_db"]).all()
+        assert (rep["xsig"] > 0).all() and (rep["xnoise"] > 0).all(), (name, rep)
+        if name not in FT4_DECODING:
+            assert len(dec) == 0, (name, dec)
+        got[name] = (ref, dec, rep)
+    for name, floor in (("clean4", None), ("blocker4", 8.0)):
+        _, dec, rep = got[name]
+        assert len(dec) == 1 and not dec["by_osd"][0] and (rep["nsync"][0], rep["nsymerr"][0]) == (16, 0), (name, dec, rep)
+        assert abs(float(rep["snr_db"][0]) - 16.0) < 0.05 if floor is None else rep["snr_db"][0] > floor, (name, rep)
+    ref, dec, rep = got["cut4_tail"]
+    early = [int(ref["recs"][int(q)]["ibest"]) < 0 for q in dec["entry"]]
+    assert len(dec) == 7 and int(dec["by_osd"].sum()) == 2 and sum(early) == 5, (dec, early)
+    assert rep["nsymerr"].min() >= 22 and rep["nsymerr"].max() <= 27 and set(rep["nsync"].tolist()) == {9, 10}, rep
+    _, dec, rep = got["cut4_head"]
+    assert len(dec) == 1 and dec["by_osd"][0] and rep["nsymerr"][0] == 29, (dec, rep)
+    # the first halves the GPU module puts through the FT4 group fetch with the GPU's own records, and the ordinary slot: no FT4 decode
+    frames = [G.oracle_frame(oracle, "FT4", G.recipe_iq(n), 0) for n in ("cut4_tail", "cut4_head")]
+    frames += [G.oracle_frame(oracle, "FT4", G.ordinary()[0], 0), G.ordinary_frame("FT4")]
+    for fr in frames:
+        assert len(G.ft4_reports(G.reference(oracle, "FT4", fr, cfg))[0]) == 0
 
 
 # ---- sensitivity: a wrong rule changes expected bytes ----------------------------------------------------------------------------------------------
