@@ -1,0 +1,223 @@
+// ap_kernels.hpp -- FT8 a-priori decoding on gfx950: the candidates belief propagation and OSD gave up on are decoded again with some of the
+// 91 message bits TOLD to the decoder -- a caller's patterns (mask + value, e.g. the bits of "CQ"), tried in the caller's order -- and the first
+// pattern under which the loop of the decode contract reaches a CRC-passing codeword that agrees with the pattern is the find.
+//
+// *** PARITY UNPINNED by the reference *** like ldpc_kernels.hpp.  The arithmetic is the one include/cwsl_gpu.h states for cwslg_ap_msg and
+// tests/ap_ref.py restates in numpy, BIT FOR BIT.  The patterns are DATA the caller loads (cwslg_set_ft8_ap): nothing here knows what a message
+// packs to.  This translation unit is built -ffp-contract=off: every product and sum below is one float32 operation.
+//
+// This is a FETCH with a kernel inside, not a stage (cwslg_fetch_ft8_ap): it reads the records the chain has left on the device and writes only
+// the group's staging.  The product library keeps one kernel per job and a test holds its count, so the a-priori work has no symbol of its own:
+// it is two further modes of ldpc_decode_kernel -- whose loop, LDS image and launch shape it shares -- behind one launch-uniform branch
+// (ApArgs::mode; ldpc_kernels.hpp), as the FT4 report is a mode of ft4_softbits_kernel:
+//   AP_DECODE    one wave per candidate, four per workgroup, grid (ceil(cap / 4), taking-part channels): the count is read on the device and the
+//                surplus waves leave.  The wave loads the graph ONCE (ldpc_graph_load: 23 values per lane, kept in registers across patterns).
+//                A pattern's six dwords of the 192-byte block are wave-uniform reads; per pattern the lane replaces the metrics of its bits l and
+//                l + 64 where the mask has them (bits 128..173 are never masked) and runs ldpc_bp_run, the ONE text of the loop, in the wave's LDS
+//                image.  A = 1.01f * max |llr| comes from a wave max reduction (exact in any order).  On success nharderr and dmin are taken
+//                against the ORIGINAL metrics: dmin is OSD's ordered chain (osd_dist over the error pattern, |llr| in the LDS image the loop has
+//                left), not a tree.  No cross-wave traffic, no workgroup barrier, every exit wave-uniform.  So that the hosting kernel keeps its
+//                registers (and the decode launch its occupancy), nothing but the graph stays live across a run: the original metrics of bits l and
+//                l + 64 are read again per pattern, A and the pattern words are scalars.
+//                Two ways of finding llr and out: desc != nullptr, candidate q of channel blockIdx.y behind the gate of the contract (its decode
+//                record attempted without crc_ok, its OSD record -- where used -- without crc_ok, nsync >= min_nsync), 20-byte record to
+//                ap[q] and dmin to dmin[q];  desc == nullptr, cwslg_ap_decode: n_flat sets from llr_flat, no gate, 24-byte cwslg_ap_msg.
+//   AP_ANNOTATE  one thread per record decode_harvest_kernel has emitted from the AP records: the record's channel through `offsets` (as the
+//                report mode finds it), then by_osd = 2, set = the pattern index, dmin = the AP record's.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "ap_host.hpp"
+#include "ldpc_kernels.hpp"
+#include "osd_kernels.hpp"
+#include "harvest_kernels.hpp"
+
+namespace cwslg {
+
+struct ApMsgRec { Ft8MsgRec msg; float dmin; };                                  // = cwslg_ap_msg
+static_assert(sizeof(ApMsgRec) == 24, "cwslg_ap_msg is 24 bytes");
+
+// One channel that takes part, built by the host under the context mutex (same index as the call's HarvestDesc array).
+struct alignas(16) ApDesc {
+    const int *cnt;          // the list's count
+    const void *soft;        // Ft8SoftRec[cap]
+    const void *msg;         // Ft8MsgRec[cap]
+    const void *osd;         // OsdRec[cap]; null: the OSD records are not used
+    void *ap;                // out: Ft8MsgRec[cap], what the harvest reads as the channel's decode records
+    float *dmin;             // out: [cap]
+    int cap;                 // the list limit the arrays were sized for
+    int pad_[3];
+};
+static_assert(sizeof(ApDesc) == 64, "descriptor layout");
+
+// a wave-uniform pointer, held in scalar registers
+template <typename T>
+__device__ __forceinline__ T *ap_uniform(T *p)
+{
+    const uintptr_t v = (uintptr_t)p;
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+    return (T *)(((uintptr_t)hi << 32) | lo);
+}
+
+__device__ __forceinline__ void ap_annotate(const ApArgs &ap)
+{
+    CWSLG_GLOBAL unsigned *g_out = as_global_rw(ap.out);
+    const CWSLG_GLOBAL unsigned *g_offsets = as_global(ap.offsets);
+    const unsigned n_emit = min(g_out[0], (unsigned)max(ap.max_out, 0));
+    const unsigned p = blockIdx.x * (unsigned)(64 * LDPC_WAVES) + threadIdx.x;
+    if (p >= n_emit) return;
+    // the record's channel: the last c with offsets[c] <= p (offsets[0] = 0; channels without decodes make equal offsets)
+    int lo_c = 0, hi_c = ap.n_chan;
+    while (hi_c - lo_c > 1) {
+        const int mid = (lo_c + hi_c) >> 1;
+        if (g_offsets[mid] <= p) lo_c = mid; else hi_c = mid;
+    }
+    const CWSLG_GLOBAL ApDesc *d = as_global(reinterpret_cast<const ApDesc *>(ap.desc)) + lo_c;
+    CWSLG_GLOBAL unsigned *rec = g_out + HARVEST_HEAD_WORDS + (size_t)p * HARVEST_REC_WORDS;
+    const unsigned entry = rec[1] & 0xffffu;                   // (< cap: the harvest walked min(count, cap) entries)
+    const unsigned w4 = as_global(reinterpret_cast<const unsigned *>(d->ap))[(size_t)entry * 5u + 4u];      // nharderr | crc_ok << 16 | pad_ << 24
+    rec[1] = entry | 2u << 16 | (w4 >> 24) << 24;
+    rec[8] = as_global(reinterpret_cast<const unsigned *>(d->dmin))[entry];
+}
+
+// (declared in ldpc_kernels.hpp, in front of the kernel that calls it; s_v, s_z: the calling wave's LDS image)
+__device__ __forceinline__ void ap_modes(const ApArgs &ap, const float *llr_flat, int n_flat, int max_iter, int min_nsync, const LdpcTables *tables,
+                                         float *s_v, float *s_z)
+{
+    if (ap.mode == AP_ANNOTATE) {
+        ap_annotate(ap);
+        return;
+    }
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int q = (int)blockIdx.x * LDPC_WAVES + wv;
+    const CWSLG_GLOBAL float *llr;
+    CWSLG_GLOBAL uint32_t *ow, *od;                            // the 20-byte record, the dmin word
+    bool attempt = true;
+    if (ap.desc) {
+        const CWSLG_GLOBAL ApDesc *d = as_global(reinterpret_cast<const ApDesc *>(ap.desc)) + blockIdx.y;
+        const int ncand = min(*as_global(d->cnt), d->cap);
+        if (q >= ncand) return;                                // wave-uniform
+        const CWSLG_GLOBAL Ft8SoftRec *rec = as_global(reinterpret_cast<const Ft8SoftRec *>(d->soft)) + q;
+        const CWSLG_GLOBAL Ft8MsgRec *m = as_global(reinterpret_cast<const Ft8MsgRec *>(d->msg)) + q;
+        llr = rec->llr;
+        ow = reinterpret_cast<CWSLG_GLOBAL uint32_t *>(as_global_rw(reinterpret_cast<Ft8MsgRec *>(d->ap)) + q);
+        od = reinterpret_cast<CWSLG_GLOBAL uint32_t *>(as_global_rw(d->dmin) + q);
+        attempt = m->iters >= 0 && m->crc_ok == 0 && rec->nsync >= min_nsync;
+        if (attempt && d->osd != nullptr) attempt = (as_global(reinterpret_cast<const OsdRec *>(d->osd)) + q)->crc_ok == 0;
+    } else {
+        if (q >= n_flat) return;
+        llr = as_global(llr_flat) + (size_t)q * LDPC_N;
+        ow = reinterpret_cast<CWSLG_GLOBAL uint32_t *>(as_global_rw(reinterpret_cast<ApMsgRec *>(ap.ap_flat)) + q);
+        od = ow + 5;
+    }
+    llr = ap_uniform(llr); ow = ap_uniform(ow); od = ap_uniform(od);
+    const bool third = lane + 128 < LDPC_N;
+    float l2 = 0.0f, amax = 0.0f;
+    if (attempt) {                                             // wave-uniform
+        const float l0 = llr[lane], l1 = llr[lane + 64];
+        l2 = third ? llr[lane + 128] : 0.0f;
+        const float a0 = fabsf(l0), a1 = fabsf(l1), a2 = fabsf(l2);
+        if (__ballot(!(a0 < INFINITY) || !(a1 < INFINITY) || !(a2 < INFINITY)) != 0ull) attempt = false;
+        amax = fmaxf(fmaxf(a0, a1), a2);
+    }
+    if (!attempt) {                                            // the decode record's "not attempted" bytes, pad_ = 0xff, dmin = +0
+        if (lane < 5) ow[lane] = lane < 3 ? 0u : lane == 3 ? 0xffffffffu : 0xff00ffffu;
+        if (lane == 5) od[0] = 0u;
+        return;
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off, 64));
+    const float A = __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(1.01f * amax)));
+
+    LdpcGraph g;
+    ldpc_graph_load(g, as_global(tables), lane);
+    const CWSLG_GLOBAL uint32_t *pw = as_global(reinterpret_cast<const uint32_t *>(ap.pats));
+
+    int iters_sum = 0, it = 0, nbad = 0, found = -1;
+    uint64_t b0 = 0ull, b1 = 0ull, b2 = 0ull, hi = 0ull;       // the word of the last run as ballots: scalars, nothing per lane outlives a run
+    for (int p = 0; p < ap.n_pat; ++p) {                       // wave-uniform
+        uint32_t w[AP_PAT_WORDS];
+#pragma unroll
+        for (int k = 0; k < AP_PAT_WORDS; ++k) w[k] = (uint32_t)__builtin_amdgcn_readfirstlane((int)pw[AP_PAT_WORDS * p + k]);
+        const uint64_t mlo = w[0] | ((uint64_t)w[1] << 32), mhi = w[2], vlo = w[3] | ((uint64_t)w[4] << 32), vhi = w[5];
+        int ln = lane;
+        asm volatile("" : "+v"(ln));                           // (the lane's shifts and addresses are made here, per pattern, not kept across the runs)
+        const bool m0 = (mlo >> ln) & 1ull, v0 = (vlo >> ln) & 1ull;
+        const bool m1 = ln < 32 && ((mhi >> (ln & 31)) & 1ull), v1 = ln < 32 && ((vhi >> (ln & 31)) & 1ull);
+        const float p0 = m0 ? (v0 ? A : -A) : llr[ln], p1 = m1 ? (v1 ? A : -A) : llr[ln + 64];
+        float z0, z1, z2;
+        ldpc_bp_run(g, p0, p1, l2, max_iter, s_v, s_z, lane, it, nbad, z0, z1, z2);
+        iters_sum += it;
+        b0 = __ballot(z0 > 0.0f);
+        b1 = __ballot(z1 > 0.0f);
+        b2 = __ballot(third && z2 > 0.0f);
+        hi = b1 & ((1ull << (LDPC_K - 64)) - 1);              // codeword bits 64..90
+        // success: a codeword, the CRC-14 rule, and the word agrees with the hypothesis it was found under
+        if (nbad == 0 && ((b0 ^ vlo) & mlo) == 0ull && ((hi ^ vhi) & mhi) == 0ull && ldpc_crc14(b0, hi) == ldpc_crc_field(b0, hi)) {
+            found = p;
+            break;
+        }
+    }
+    if (found < 0) {                                           // zero bits, iters = the sum, nbad = the last run's, nharderr -1, crc_ok 0, pad_ 0xff
+        if (lane < 5) ow[lane] = lane < 3 ? 0u : lane == 3 ? (((uint32_t)iters_sum & 0xffffu) | ((uint32_t)nbad << 16)) : 0xff00ffffu;
+        if (lane == 5) od[0] = 0u;
+        return;
+    }
+    // nharderr and dmin against the ORIGINAL metrics, read once more: the error pattern in OSD's bit layout, |llr| where the loop's z image was
+    const float l0 = llr[lane], l1 = llr[lane + 64];
+    const uint64_t e0 = __ballot(l0 > 0.0f) ^ b0, e1 = __ballot(l1 > 0.0f) ^ b1, e2 = __ballot(third && l2 > 0.0f) ^ b2;
+    const int nharderr = __popcll(e0) + __popcll(e1) + __popcll(e2);
+    const uint32_t e[OSD_GW] = {(uint32_t)e0, (uint32_t)(e0 >> 32), (uint32_t)e1, (uint32_t)(e1 >> 32), (uint32_t)e2, (uint32_t)(e2 >> 32)};
+    ldpc_wave_sync();                                          // (every lane has read its rows' z)
+    s_z[lane] = fabsf(l0);
+    s_z[lane + 64] = fabsf(l1);
+    s_z[lane + 128] = fabsf(l2);                               // (174..191: +0, never read: the error pattern has no bit there)
+    ldpc_wave_sync();
+    const float dmin = osd_dist(e, s_z);                       // wave-uniform: every lane walks the same chain
+    const uint64_t r0 = __brevll(b0), r1 = __brevll(hi);       // bits[] as cwslg_ft8_msg packs them
+    uint32_t word;
+    switch (lane) {
+    case 0: word = __builtin_bswap32((uint32_t)(r0 >> 32)); break;
+    case 1: word = __builtin_bswap32((uint32_t)r0); break;
+    case 2: word = __builtin_bswap32((uint32_t)(r1 >> 32)); break;
+    case 3: word = (uint32_t)it & 0xffffu; break;             // iters of that run, nbad = 0
+    default: word = ((uint32_t)nharderr & 0xffffu) | 0x10000u | ((uint32_t)found << 24); break;
+    }
+    if (lane < 5) ow[lane] = word;
+    if (lane == 5) od[0] = __float_as_uint(dmin);
+}
+
+// The launches of the a-priori modes: ldpc_decode_kernel with the decode's own arguments null / 0.  The caller asks hipGetLastError.
+inline void ap_launch(hipStream_t s, dim3 grid, const float *llr, int n_flat, int max_iter, int min_nsync, const void *tables, const ApArgs &ap)
+{
+    hipLaunchKernelGGL(ldpc_decode_kernel, grid, dim3(64 * LDPC_WAVES), 0, s, (const SyncWork *)nullptr, (Ft8SoftRec *const *)nullptr, (Ft8MsgRec *const *)nullptr,
+                       llr, (Ft8MsgRec *)nullptr, n_flat, 0, max_iter, min_nsync, (const LdpcTables *)tables, (const Ft4Work *)nullptr,
+                       (Ft4SoftRec *const *)nullptr, (Ft4MsgRec *const *)nullptr, 0, ap);
+}
+//   AP_DECODE on the n_chan channels of d_desc (cap_max: the largest cap among them)
+inline void ap_launch_chain(hipStream_t s, const ApDesc *d_desc, int n_chan, int cap_max, int max_iter, int min_nsync, const void *tables,
+                            const void *pats, int n_pat)
+{
+    if (n_chan <= 0 || cap_max <= 0) return;
+    ApArgs ap{};
+    ap.mode = AP_DECODE; ap.n_pat = n_pat; ap.desc = d_desc; ap.pats = pats; ap.n_chan = n_chan;
+    ap_launch(s, dim3((unsigned)((cap_max + LDPC_WAVES - 1) / LDPC_WAVES), (unsigned)n_chan), nullptr, 0, max_iter, min_nsync, tables, ap);
+}
+//   AP_DECODE flat: n sets of 174 metrics, no gate
+inline void ap_launch_flat(hipStream_t s, const void *tables, const void *pats, int n_pat, const float *llr, ApMsgRec *out, int n, int max_iter)
+{
+    if (n <= 0) return;
+    ApArgs ap{};
+    ap.mode = AP_DECODE; ap.n_pat = n_pat; ap.pats = pats; ap.ap_flat = out;
+    ap_launch(s, dim3((unsigned)((n + LDPC_WAVES - 1) / LDPC_WAVES), 1), llr, n, max_iter, 0, tables, ap);
+}
+//   AP_ANNOTATE behind harvest_launch on the same stream and blocks: a thread per record that emit may have written
+inline void ap_launch_annotate(hipStream_t s, const ApDesc *d_desc, const unsigned *d_offsets, unsigned *d_out, int n_chan, int lim)
+{
+    if (lim <= 0) return;
+    ApArgs ap{};
+    ap.mode = AP_ANNOTATE; ap.desc = d_desc; ap.offsets = d_offsets; ap.out = d_out; ap.n_chan = n_chan; ap.max_out = lim;
+    ap_launch(s, dim3((unsigned)((lim + 64 * LDPC_WAVES - 1) / (64 * LDPC_WAVES))), nullptr, 0, 0, 0, nullptr, ap);
+}
+
+} // namespace cwslg

@@ -53,6 +53,7 @@
 #include "ft4soft_kernels.hpp"
 #include "longsync_kernels.hpp"
 #include "harvest_kernels.hpp"
+#include "ap_kernels.hpp"
 
 namespace cwslg {
 
@@ -225,6 +226,10 @@ struct HarvestStage {
     std::mutex mu;
     char *h = nullptr, *d = nullptr;
     size_t h_bytes = 0, d_bytes = 0;
+    // cwslg_fetch_ft8_ap (ap_kernels.hpp; the FT8 group's stage only): per taking-part channel cap x (20 + 4) bytes of AP records and their dmin,
+    // allocated by the first such call, grown on demand, freed by cwslg_destroy
+    char *d_ap = nullptr;
+    size_t ap_bytes = 0;
 };
 
 struct TimedSpan {
@@ -1265,6 +1270,7 @@ void cwslg_destroy(cwslg_ctx *c)
     for (HarvestStage &hs : c->harvest) {
         if (hs.h) (void)hipHostFree(hs.h);
         if (hs.d) (void)hipFree(hs.d);
+        if (hs.d_ap) (void)hipFree(hs.d_ap);
     }
     if (c->clk_h) (void)hipHostFree(c->clk_h);
     for (hipStream_t fs : c->fetch_stream) if (fs) { (void)hipStreamSynchronize(fs); (void)hipStreamDestroy(fs); }

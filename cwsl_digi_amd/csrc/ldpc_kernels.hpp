@@ -102,15 +102,91 @@ __device__ __forceinline__ void ldpc_row_update(LdpcRow &r, float *s_v, int m)
     dst[1] = v4f{r.v[4], r.v[5], r.v[6], 0.0f};       // (slot 6 of a weight-6 row and slot 7 are never read)
 }
 
+// The graph as one lane holds it across runs: the message positions of its three bits and its two rows.
+struct LdpcGraph {
+    int ep[3][3];
+    LdpcRow ra, rb;
+};
+
+__device__ __forceinline__ void ldpc_graph_load(LdpcGraph &g, const CWSLG_GLOBAL LdpcTables *tab, int lane)
+{
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+        const v2u w = *reinterpret_cast<const CWSLG_GLOBAL v2u *>(&tab->epos[lane + 64 * b][0]);
+        g.ep[b][0] = (int)(w.x & 0xffffu); g.ep[b][1] = (int)(w.x >> 16); g.ep[b][2] = (int)(w.y & 0xffffu);
+    }
+    ldpc_row_load(g.ra, tab, lane);
+    ldpc_row_load(g.rb, tab, lane + 64);
+}
+
+// The loop of the decode contract (steps 1-8 of cwslg_ft8_msg) on the metrics l0, l1, l2 of the lane's bits, in the wave's LDS image: the ONE
+// text of it, called by ldpc_decode_kernel and by its a-priori mode (ap_kernels.hpp: ap_modes), which runs it once per pattern.  A run starts from messages
+// +0 whatever an earlier run of the wave left; at exit it = iters, nbad, and z0, z1, z2 the lane's z (cw = z > 0).
+__device__ __forceinline__ void ldpc_bp_run(LdpcGraph &g, float l0, float l1, float l2, int max_iter, float *s_v, float *s_z, int lane, int &it_out,
+                                            int &nbad_out, float &z0, float &z1, float &z2)
+{
+    const bool third = lane + 128 < LDPC_N;
+#pragma unroll
+    for (int e = 0; e < LDPC_ROWMAX; ++e) g.ra.v[e] = g.rb.v[e] = 0.0f;
+    for (int k = lane; k < LDPC_VSIZE; k += 64) s_v[k] = 0.0f;
+    s_z[lane + 128] = 0.0f;                                    // 128..191: bits 128..173 are rewritten below, the rest stays +0
+    ldpc_wave_sync();
+
+    int ncnt = 0, nclast = 0, it = 0, nbad = 0;
+    for (;;) {
+        z0 = ((l0 + s_v[g.ep[0][0]]) + s_v[g.ep[0][1]]) + s_v[g.ep[0][2]];
+        z1 = ((l1 + s_v[g.ep[1][0]]) + s_v[g.ep[1][1]]) + s_v[g.ep[1][2]];
+        z2 = ((l2 + s_v[g.ep[2][0]]) + s_v[g.ep[2][1]]) + s_v[g.ep[2][2]];
+        s_z[lane] = z0;
+        s_z[lane + 64] = z1;
+        if (third) s_z[lane + 128] = z2;
+        ldpc_wave_sync();
+        const bool odd_a = ldpc_row_parity(g.ra, s_z), odd_b = ldpc_row_parity(g.rb, s_z);
+        nbad = __popcll(__ballot(odd_a)) + __popcll(__ballot(odd_b));
+        if (nbad == 0 || it == max_iter) break;
+        if (it > 0) {
+            ncnt = nbad - nclast < 0 ? 0 : ncnt + 1;
+            if (ncnt >= 5 && it >= 10 && nbad > 15) break;
+        }
+        nclast = nbad;
+        ldpc_row_update(g.ra, s_v, lane);
+        ldpc_row_update(g.rb, s_v, lane + 64);
+        ldpc_wave_sync();
+        ++it;
+    }
+    it_out = it;
+    nbad_out = nbad;
+}
+
+// FT8 a-priori decoding (ap_kernels.hpp) runs as further modes of THIS symbol -- the product library keeps one kernel per job and its count is
+// held by a test -- behind one launch-uniform branch at the top: the three addressing modes above never see more of it than that branch.
+struct ApArgs {
+    int mode;                          // AP_OFF: the decode; AP_DECODE / AP_ANNOTATE: ap_kernels.hpp
+    int n_pat;
+    const void *desc;                  // ApDesc[n_chan], or null: llr_flat / ap_flat
+    const void *pats;                  // ApBlock
+    void *ap_flat;                     // ApMsgRec[n_flat]
+    const unsigned *offsets;           // AP_ANNOTATE: the harvest's offsets and output block
+    unsigned *out;
+    int n_chan, max_out;
+};
+constexpr int AP_OFF = 0, AP_DECODE = 1, AP_ANNOTATE = 2;
+__device__ __forceinline__ void ap_modes(const ApArgs &ap, const float *llr_flat, int n_flat, int max_iter, int min_nsync, const LdpcTables *tables,
+                                         float *s_v, float *s_z);
+
 __global__ __launch_bounds__(64 * LDPC_WAVES) void ldpc_decode_kernel(const SyncWork *__restrict__ works, Ft8SoftRec *const *__restrict__ soft,
                                                                       Ft8MsgRec *const *__restrict__ msg, const float *__restrict__ llr_flat,
                                                                       Ft8MsgRec *__restrict__ out_flat, int n_flat, int maxcand, int max_iter, int min_nsync,
                                                                       const LdpcTables *__restrict__ tables, const Ft4Work *__restrict__ works4,
                                                                       Ft4SoftRec *const *__restrict__ soft4, Ft4MsgRec *const *__restrict__ msg4,
-                                                                      int min_nqual)
+                                                                      int min_nqual, ApArgs ap)
 {
     __shared__ __attribute__((aligned(16))) float s_vall[LDPC_WAVES][LDPC_VSIZE];
     __shared__ __attribute__((aligned(16))) float s_zall[LDPC_WAVES][192];
+    if (ap.mode != AP_OFF) {                                   // uniform over the launch
+        ap_modes(ap, llr_flat, n_flat, max_iter, min_nsync, tables, s_vall[threadIdx.x >> 6], s_zall[threadIdx.x >> 6]);
+        return;
+    }
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int q = (int)blockIdx.x * LDPC_WAVES + wv;
     const CWSLG_GLOBAL float *llr;
@@ -148,42 +224,11 @@ __global__ __launch_bounds__(64 * LDPC_WAVES) void ldpc_decode_kernel(const Sync
     const CWSLG_GLOBAL LdpcTables *tab = as_global(tables);
     const bool third = lane + 128 < LDPC_N;
     const float l0 = llr[lane], l1 = llr[lane + 64], l2 = third ? llr[lane + 128] : 0.0f;
-    int ep[3][3];
-#pragma unroll
-    for (int b = 0; b < 3; ++b) {
-        const v2u w = *reinterpret_cast<const CWSLG_GLOBAL v2u *>(&tab->epos[lane + 64 * b][0]);
-        ep[b][0] = (int)(w.x & 0xffffu); ep[b][1] = (int)(w.x >> 16); ep[b][2] = (int)(w.y & 0xffffu);
-    }
-    LdpcRow ra, rb;
-    ldpc_row_load(ra, tab, lane);
-    ldpc_row_load(rb, tab, lane + 64);
-    for (int k = lane; k < LDPC_VSIZE; k += 64) s_v[k] = 0.0f;
-    s_z[lane + 128] = 0.0f;                                    // 128..191: bits 128..173 are rewritten below, the rest stays +0
-    ldpc_wave_sync();
-
-    int ncnt = 0, nclast = 0, it = 0, nbad = 0;
+    LdpcGraph g;
+    ldpc_graph_load(g, tab, lane);
+    int it, nbad;
     float z0, z1, z2;
-    for (;;) {
-        z0 = ((l0 + s_v[ep[0][0]]) + s_v[ep[0][1]]) + s_v[ep[0][2]];
-        z1 = ((l1 + s_v[ep[1][0]]) + s_v[ep[1][1]]) + s_v[ep[1][2]];
-        z2 = ((l2 + s_v[ep[2][0]]) + s_v[ep[2][1]]) + s_v[ep[2][2]];
-        s_z[lane] = z0;
-        s_z[lane + 64] = z1;
-        if (third) s_z[lane + 128] = z2;
-        ldpc_wave_sync();
-        const bool odd_a = ldpc_row_parity(ra, s_z), odd_b = ldpc_row_parity(rb, s_z);
-        nbad = __popcll(__ballot(odd_a)) + __popcll(__ballot(odd_b));
-        if (nbad == 0 || it == max_iter) break;
-        if (it > 0) {
-            ncnt = nbad - nclast < 0 ? 0 : ncnt + 1;
-            if (ncnt >= 5 && it >= 10 && nbad > 15) break;
-        }
-        nclast = nbad;
-        ldpc_row_update(ra, s_v, lane);
-        ldpc_row_update(rb, s_v, lane + 64);
-        ldpc_wave_sync();
-        ++it;
-    }
+    ldpc_bp_run(g, l0, l1, l2, max_iter, s_v, s_z, lane, it, nbad, z0, z1, z2);
 
     const bool c0 = z0 > 0.0f, c1 = z1 > 0.0f, c2 = third && z2 > 0.0f;
     const uint64_t b0 = __ballot(c0), b1 = __ballot(c1);
@@ -204,3 +249,5 @@ __global__ __launch_bounds__(64 * LDPC_WAVES) void ldpc_decode_kernel(const Sync
 }
 
 } // namespace cwslg
+
+#include "ap_kernels.hpp"              // ap_modes: every translation unit that has the kernel has its a-priori modes

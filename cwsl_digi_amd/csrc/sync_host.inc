@@ -148,14 +148,14 @@ void ldpc_launch_ft8(hipStream_t st, const void *tables, const SyncWork *works, 
 {
     hipLaunchKernelGGL(ldpc_decode_kernel, dim3((unsigned)((max_cand + LDPC_WAVES - 1) / LDPC_WAVES), (unsigned)n_chan), dim3(64 * LDPC_WAVES), 0, st, works, soft, msg,
                        (const float *)nullptr, (Ft8MsgRec *)nullptr, 0, max_cand, max_iter, min_nsync, (const LdpcTables *)tables, (const Ft4Work *)nullptr,
-                       (Ft4SoftRec *const *)nullptr, (Ft4MsgRec *const *)nullptr, 0);
+                       (Ft4SoftRec *const *)nullptr, (Ft4MsgRec *const *)nullptr, 0, ApArgs{});
 }
 //   flat: n sets of 174 metrics, no gate
 void ldpc_launch_flat(hipStream_t st, const void *tables, const float *llr, Ft8MsgRec *out, int n, int max_iter)
 {
     hipLaunchKernelGGL(ldpc_decode_kernel, dim3((unsigned)((n + LDPC_WAVES - 1) / LDPC_WAVES), 1), dim3(64 * LDPC_WAVES), 0, st, (const SyncWork *)nullptr,
                        (Ft8SoftRec *const *)nullptr, (Ft8MsgRec *const *)nullptr, llr, out, n, 0, max_iter, 0, (const LdpcTables *)tables, (const Ft4Work *)nullptr,
-                       (Ft4SoftRec *const *)nullptr, (Ft4MsgRec *const *)nullptr, 0);
+                       (Ft4SoftRec *const *)nullptr, (Ft4MsgRec *const *)nullptr, 0, ApArgs{});
 }
 //   FT4 chain: one wave per (record slot, metric set) of n_chan channels, 9 max_cand waves per channel
 void ldpc_launch_ft4(hipStream_t st, const void *tables, const Ft4Work *works4, Ft4SoftRec *const *soft4, Ft4MsgRec *const *msg4, size_t n_chan, int max_cand,
@@ -163,7 +163,7 @@ void ldpc_launch_ft4(hipStream_t st, const void *tables, const Ft4Work *works4, 
 {
     hipLaunchKernelGGL(ldpc_decode_kernel, dim3((unsigned)((9 * max_cand + LDPC_WAVES - 1) / LDPC_WAVES), (unsigned)n_chan), dim3(64 * LDPC_WAVES), 0, st,
                        (const SyncWork *)nullptr, (Ft8SoftRec *const *)nullptr, (Ft8MsgRec *const *)nullptr, (const float *)nullptr, (Ft8MsgRec *)nullptr, 0, max_cand,
-                       max_iter, min_nsync, (const LdpcTables *)tables, works4, soft4, msg4, min_nqual);
+                       max_iter, min_nsync, (const LdpcTables *)tables, works4, soft4, msg4, min_nqual, ApArgs{});
 }
 
 // osd_decode_kernel's three addressing modes
@@ -720,6 +720,8 @@ int cwslg_set_ldpc_code(cwslg_ctx *c, const uint8_t *nm)
     if (!c->sync_shared.d_ldpc) HIPCHK(c, hipMalloc(&c->sync_shared.d_ldpc, sizeof(LdpcTables)));
     HIPCHK(c, sync_streams(c));                                // no queued decode launch may still read the old tables
     HIPCHK(c, hipMemcpy(c->sync_shared.d_ldpc, &t, sizeof(LdpcTables), hipMemcpyHostToDevice));
+    static_assert(sizeof(c->sync_shared.ldpc_tables) == sizeof(LdpcTables), "table block");
+    std::memcpy(c->sync_shared.ldpc_tables, &t, sizeof(LdpcTables));
     c->sync_shared.ldpc_loaded = true;
     c->sync_shared.osd_ready = false;
     // the systematic encoder of the decode reports: host bytes only (the device copy is made by the first cwslg_fetch_decode_reports after this
@@ -836,6 +838,58 @@ int cwslg_osd_decode(cwslg_ctx *c, const float *llr, int n, int order, cwslg_osd
     return CWSLG_OK;
 }
 
+// FT8 a-priori decoding (ap_kernels.hpp).  The patterns are the caller's data: validated and packed on the host (ap_host.hpp), host bytes only --
+// every AP call takes the block in force at the call up with its own upload, so nothing queued ever reads a block that a later set replaces.
+int cwslg_set_ft8_ap(cwslg_ctx *c, const cwslg_ap_pattern *pat, int n_pat, int max_iter, int min_nsync)
+{
+    static_assert(sizeof(cwslg_ap_pattern) == sizeof(ApPattern), "pattern layout");
+    if (!c) return CWSLG_ERR_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    if (max_iter < 1 || max_iter > 200 || min_nsync < 0 || min_nsync > 22) return fail(c, CWSLG_ERR_ARG, "FT8 AP parameters out of range");
+    ApBlock b;
+    const int why = ap_pack(reinterpret_cast<const ApPattern *>(pat), n_pat, &b);
+    if (why) {
+        static const char *const reason[] = {"", "n_pat outside 0..8, or no pattern array", "a mask or value bit at position 91..95", "a value bit outside its mask"};
+        return fail(c, CWSLG_ERR_ARG, "AP patterns rejected: %s", reason[why]);
+    }
+    SyncShared &s = c->sync_shared;
+    static_assert(sizeof(s.ap_block) == sizeof(ApBlock), "pattern block");
+    std::memcpy(s.ap_block, &b, sizeof(ApBlock));
+    s.ap_npat = n_pat; s.ap_max_iter = max_iter; s.ap_min_nsync = min_nsync;
+    return CWSLG_OK;
+}
+
+// The a-priori decode (ap_kernels.hpp: a mode of ldpc_decode_kernel) on n sets of 174 metrics from host memory, no gate; synchronous (temporary device buffers, the context's stream).  The
+// patterns and the tables of the code go up in front of the metrics: in | pattern block | tables | metrics | records.
+int cwslg_ap_decode(cwslg_ctx *c, const float *llr, int n, cwslg_ap_msg *out)
+{
+    static_assert(sizeof(cwslg_ap_msg) == sizeof(ApMsgRec), "record layout");
+    if (!c || n < 0 || (n > 0 && (!llr || !out))) return CWSLG_ERR_ARG;
+    std::lock_guard<std::mutex> g(c->mu);
+    const SyncShared &s = c->sync_shared;
+    if (!s.ldpc_loaded) return fail(c, CWSLG_ERR_ARG, "no parity-check table loaded (cwslg_set_ldpc_code)");
+    if (s.ap_npat <= 0) return fail(c, CWSLG_ERR_ARG, "no AP pattern set (cwslg_set_ft8_ap)");
+    if (n == 0) return CWSLG_OK;
+    hipSetDevice(c->device);
+    const size_t pat_at = 0, tab_at = 256, llr_at = tab_at + sizeof(LdpcTables);
+    const size_t in_bytes = (size_t)n * LDPC_N * sizeof(float), out_at = llr_at + in_bytes, out_bytes = (size_t)n * sizeof(ApMsgRec);
+    char *d = nullptr;
+    HIPCHK(c, hipMalloc((void **)&d, out_at + out_bytes));      // (every part starts at a multiple of 8)
+    hipError_t e = hipMemcpyAsync(d + pat_at, s.ap_block, sizeof(ApBlock), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + tab_at, s.ldpc_tables, sizeof(LdpcTables), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + llr_at, llr, in_bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        ap_launch_flat(c->stream, d + tab_at, d + pat_at, s.ap_npat, (const float *)(d + llr_at), (ApMsgRec *)(d + out_at), n, s.ap_max_iter);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d + out_at, out_bytes, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);
+    (void)hipFree(d);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(c, CWSLG_ERR_HIP, "cwslg_ap_decode failed: %s", hipGetErrorString(e));
+    return CWSLG_OK;
+}
+
 int cwslg_enable_ft4_coherent(cwslg_ctx *c, int enable)
 {
     if (!c) return CWSLG_ERR_ARG;
@@ -928,9 +982,14 @@ int cwslg_fetch_ft4_osd(cwslg_ctx *c, int ch_id, cwslg_ft4_osd *dst, int max, in
 // records_queued queues it only behind REC_SOFT4 and REC_FT4SYNC, i.e. with ft4_coherent on in the configuration of that boundary -- the same
 // switch under which sync_launch runs ft4_dft567 / ft4_fft64_unpack on the channel's Ft4Work (cx = d_cx).  d_cx therefore holds THAT frame's
 // spectrum, and the sync records read here are that boundary's too: no path hands a stale spectrum to the report.
+// a-priori (cwslg_fetch_ft8_ap, FT8 only; ap_kernels.hpp): an ApDesc per channel, the pattern block and the tables of the code in force go up
+// behind the HarvestDesc array in the same copy; the a-priori decode (a mode of ldpc_decode_kernel) runs IN FRONT of the three harvest launches and leaves a decode-record array
+// per channel in the group's AP staging, which is what HarvestDesc.msg then points at (.osd null); one annotate launch follows them.
+enum { FETCH_DECODES = 0, FETCH_REPORTS = 1, FETCH_AP = 2 };
 static int fetch_decodes_impl(cwslg_ctx *c, int group, uint64_t *start_epoch, cwslg_decode *dst, cwslg_decode_report *rep, int max, int *n, int *n_total,
-                              int *n_channels, bool reports)
+                              int *n_channels, int what)
 {
+    const bool reports = what == FETCH_REPORTS, ap = what == FETCH_AP;
     static_assert(sizeof(cwslg_decode) == HARVEST_REC_WORDS * sizeof(unsigned), "record layout");
     static_assert(sizeof(cwslg_decode_report) == sizeof(ReportRec), "record layout");
     const bool ft4 = group == CWSLG_GROUP_FT4;
@@ -942,6 +1001,10 @@ static int fetch_decodes_impl(cwslg_ctx *c, int group, uint64_t *start_epoch, cw
     std::vector<HarvestDesc> descs;
     std::vector<ReportDesc> rdescs;
     std::vector<Ft4ReportDesc> rdescs4;
+    std::vector<ApDesc> adescs;
+    ApBlock ap_block{};
+    LdpcTables ap_tables{};
+    int ap_npat = 0, ap_max_iter = 0, ap_min_nsync = 0, ap_cap_max = 0;
     Ft4Tables tb4{};
     const float2 *d_w32 = nullptr;
     const uint32_t *d_enc = nullptr;
@@ -952,6 +1015,14 @@ static int fetch_decodes_impl(cwslg_ctx *c, int group, uint64_t *start_epoch, cw
         if (reports && !c->sync_shared.enc_ready)
             return fail(c, CWSLG_ERR_ARG, "%s", c->sync_shared.ldpc_loaded ? "decode reports need a systematic code: columns 91..173 of the loaded parity-check table are singular"
                                                                     : "decode reports need a parity-check table (cwslg_set_ldpc_code)");
+        if (ap) {
+            const SyncShared &s = c->sync_shared;
+            if (!s.ldpc_loaded) return fail(c, CWSLG_ERR_ARG, "a-priori decoding needs a parity-check table (cwslg_set_ldpc_code)");
+            if (s.ap_npat <= 0) return fail(c, CWSLG_ERR_ARG, "no AP pattern set (cwslg_set_ft8_ap)");
+            std::memcpy(&ap_block, s.ap_block, sizeof(ApBlock));
+            std::memcpy(&ap_tables, s.ldpc_tables, sizeof(LdpcTables));
+            ap_npat = s.ap_npat; ap_max_iter = s.ap_max_iter; ap_min_nsync = s.ap_min_nsync;
+        }
         uint64_t E = *start_epoch;
         std::vector<std::pair<int, uint64_t>> live;
         for (size_t id = 0; id < c->chans.size(); ++id) {
@@ -976,7 +1047,16 @@ static int fetch_decodes_impl(cwslg_ctx *c, int group, uint64_t *start_epoch, cw
             d.ch_id = l.first;
             descs.push_back(d);
             bound += (size_t)d.cap * (ft4 ? 3 : 1);
-            if (reports && ft4) {
+            if (ap) {           // (the staging pointers are filled in below, once its size is known)
+                ApDesc a{};
+                a.cnt = b.d_ncand;
+                a.soft = b.d_soft;
+                a.msg = d.msg;
+                a.osd = d.osd;
+                a.cap = d.cap;
+                adescs.push_back(a);
+                ap_cap_max = std::max(ap_cap_max, d.cap);
+            } else if (reports && ft4) {
                 Ft4ReportDesc r{};
                 r.cx = b.d_cx;
                 r.rec = (const Ft4Rec *)b.d_rec;
@@ -1007,6 +1087,27 @@ static int fetch_decodes_impl(cwslg_ctx *c, int group, uint64_t *start_epoch, cw
             tb4 = c->ft4_tables;            // (FT4: built by the boundary that made the records)
             d_w32 = s.ft4_w32;
         }
+        if (ap) {
+            // the group's AP staging: per channel cap records of 20 bytes, then cap dmin words, each channel from a multiple of 16.  Only calls
+            // that hs.mu serialises and that synchronise before they return touch it: none is in flight now
+            size_t need = 0;
+            for (const ApDesc &a : adescs) need += ((size_t)a.cap * (sizeof(Ft8MsgRec) + sizeof(float)) + 15) & ~size_t(15);
+            if (hs.ap_bytes < need) {
+                if (hs.d_ap) (void)hipFree(hs.d_ap);
+                hs.d_ap = nullptr; hs.ap_bytes = 0;
+                HIPCHK(c, hipMalloc((void **)&hs.d_ap, need + need / 2));
+                hs.ap_bytes = need + need / 2;
+            }
+            size_t at = 0;
+            for (size_t i = 0; i < adescs.size(); ++i) {
+                ApDesc &a = adescs[i];
+                a.ap = hs.d_ap + at;
+                a.dmin = (float *)(hs.d_ap + at + (size_t)a.cap * sizeof(Ft8MsgRec));
+                at += ((size_t)a.cap * (sizeof(Ft8MsgRec) + sizeof(float)) + 15) & ~size_t(15);
+                descs[i].msg = a.ap;
+                descs[i].osd = nullptr;
+            }
+        }
         *start_epoch = E;
         const int rc = begin_result_fetch(c, c->chans[descs[0].ch_id], rf);
         if (rc) return rc;
@@ -1016,7 +1117,9 @@ static int fetch_decodes_impl(cwslg_ctx *c, int group, uint64_t *start_epoch, cw
     auto pad = [](size_t v) { return (v + 255) & ~size_t(255); };
     const size_t desc_bytes = nch * sizeof(HarvestDesc), cnt_bytes = pad(nch * sizeof(unsigned));
     const size_t rdesc_bytes = ft4 ? rdescs4.size() * sizeof(Ft4ReportDesc) : rdescs.size() * sizeof(ReportDesc);
-    const size_t up_bytes = reports ? pad(desc_bytes) + rdesc_bytes : desc_bytes, up_pad = pad(up_bytes);
+    // a-priori: | HarvestDesc | ApDesc | pattern block | tables |, each from a multiple of 256
+    const size_t adesc_at = pad(desc_bytes), apat_at = adesc_at + pad(adescs.size() * sizeof(ApDesc)), atab_at = apat_at + pad(sizeof(ApBlock));
+    const size_t up_bytes = ap ? atab_at + sizeof(LdpcTables) : reports ? pad(desc_bytes) + rdesc_bytes : desc_bytes, up_pad = pad(up_bytes);
     // down: head | lim records | (reports: from the next 16-byte boundary) lim reports
     const size_t rec_words = HARVEST_HEAD_WORDS + lim * HARVEST_REC_WORDS, rep_at = (rec_words + 3) & ~size_t(3);
     const size_t out_bytes = (reports ? rep_at + lim * REPORT_WORDS : rec_words) * sizeof(unsigned);
@@ -1035,13 +1138,20 @@ static int fetch_decodes_impl(cwslg_ctx *c, int group, uint64_t *start_epoch, cw
     }
     std::memcpy(hs.h, descs.data(), desc_bytes);
     if (reports) std::memcpy(hs.h + pad(desc_bytes), ft4 ? (const void *)rdescs4.data() : (const void *)rdescs.data(), rdesc_bytes);
+    if (ap) {
+        std::memcpy(hs.h + adesc_at, adescs.data(), adescs.size() * sizeof(ApDesc));
+        std::memcpy(hs.h + apat_at, &ap_block, sizeof(ApBlock));
+        std::memcpy(hs.h + atab_at, &ap_tables, sizeof(LdpcTables));
+    }
     unsigned *h_out = (unsigned *)(hs.h + up_pad);
     const HarvestDesc *d_desc = (const HarvestDesc *)hs.d;
     unsigned *d_counts = (unsigned *)(hs.d + up_pad), *d_offsets = (unsigned *)(hs.d + up_pad + cnt_bytes);
     unsigned *d_out = (unsigned *)(hs.d + up_pad + 2 * cnt_bytes);
     HIPCHK(c, hipStreamWaitEvent(rf.fs, rf.ev, 0));
     HIPCHK(c, hipMemcpyAsync(hs.d, hs.h, up_bytes, hipMemcpyHostToDevice, rf.fs));
+    if (ap) ap_launch_chain(rf.fs, (const ApDesc *)(hs.d + adesc_at), (int)nch, ap_cap_max, ap_max_iter, ap_min_nsync, hs.d + atab_at, hs.d + apat_at, ap_npat);
     harvest_launch(rf.fs, d_desc, d_counts, d_offsets, d_out, (int)nch, (int)lim, ft4 ? 1 : 0);
+    if (ap) ap_launch_annotate(rf.fs, (const ApDesc *)(hs.d + adesc_at), d_offsets, d_out, (int)nch, (int)lim);
     if (reports && ft4)
         ft4_report_launch(rf.fs, (const Ft4ReportDesc *)(hs.d + pad(desc_bytes)), d_offsets, d_out, d_enc, d_out + rep_at, tb4, d_w32, (int)nch, (int)lim);
     else if (reports)
@@ -1065,7 +1175,7 @@ int cwslg_fetch_decodes(cwslg_ctx *c, int group, uint64_t *start_epoch, cwslg_de
     if (n_channels) *n_channels = 0;
     if (!c || !start_epoch || !n || !n_total || (max > 0 && !dst)) return CWSLG_ERR_ARG;
     if (group != CWSLG_GROUP_FT8 && group != CWSLG_GROUP_FT4) return fail(c, CWSLG_ERR_ARG, "decodes exist for the FT8 and FT4 groups only (group %d)", group);
-    return fetch_decodes_impl(c, group, start_epoch, dst, nullptr, max, n, n_total, n_channels, false);
+    return fetch_decodes_impl(c, group, start_epoch, dst, nullptr, max, n, n_total, n_channels, FETCH_DECODES);
 }
 
 // The same call with a signal report per decode (harvest_kernels.hpp: HARVEST_REPORT; the contract is the header's, cwslg_decode_report).
@@ -1077,7 +1187,7 @@ int cwslg_fetch_decode_reports(cwslg_ctx *c, int group, uint64_t *start_epoch, c
     if (n_channels) *n_channels = 0;
     if (!c || !start_epoch || !n || !n_total) return CWSLG_ERR_ARG;
     if (group != CWSLG_GROUP_FT8) return fail(c, CWSLG_ERR_ARG, "decode reports exist for the FT8 group only (group %d)", group);
-    return fetch_decodes_impl(c, group, start_epoch, dec, rep, max, n, n_total, n_channels, true);
+    return fetch_decodes_impl(c, group, start_epoch, dec, rep, max, n, n_total, n_channels, FETCH_REPORTS);
 }
 
 // The FT4 group's call (ft4soft_kernels.hpp: FT4S_REPORT; the contract is the header's, "FT4 signal reports").
@@ -1088,7 +1198,18 @@ int cwslg_fetch_ft4_decode_reports(cwslg_ctx *c, uint64_t *start_epoch, cwslg_de
     if (n_total) *n_total = 0;
     if (n_channels) *n_channels = 0;
     if (!c || !start_epoch || !n || !n_total) return CWSLG_ERR_ARG;
-    return fetch_decodes_impl(c, CWSLG_GROUP_FT4, start_epoch, dec, rep, max, n, n_total, n_channels, true);
+    return fetch_decodes_impl(c, CWSLG_GROUP_FT4, start_epoch, dec, rep, max, n, n_total, n_channels, FETCH_REPORTS);
+}
+
+// The a-priori words of the FT8 group (ap_kernels.hpp; the contract is the header's, cwslg_fetch_ft8_ap): cwslg_fetch_decodes' ticket, epoch rule
+// and serialisation, with the a-priori decode launch in front of the harvest launches and one annotate launch behind them.
+int cwslg_fetch_ft8_ap(cwslg_ctx *c, uint64_t *start_epoch, cwslg_decode *dst, int max, int *n, int *n_total, int *n_channels)
+{
+    if (n) *n = 0;
+    if (n_total) *n_total = 0;
+    if (n_channels) *n_channels = 0;
+    if (!c || !start_epoch || !n || !n_total || (max > 0 && !dst)) return CWSLG_ERR_ARG;
+    return fetch_decodes_impl(c, CWSLG_GROUP_FT8, start_epoch, dst, nullptr, max, n, n_total, n_channels, FETCH_AP);
 }
 
 // The channel tones of a 91-bit word under the code in force: the re-encoder of the reports on its own, host work only.

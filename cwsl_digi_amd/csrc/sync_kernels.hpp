@@ -74,6 +74,7 @@ struct SyncShared {
     const float2 *ft4_w32 = nullptr;      // inside d_ft4c: [32] (cos, +sin) of 2 pi p / 32, ft4_softbits_kernel's symbol spectra (ft4soft_kernels.hpp)
     void *d_ldpc = nullptr;               // LdpcTables (ldpc_host.hpp) derived from the caller's parity-check table; allocated by the first cwslg_set_ldpc_code
     bool ldpc_loaded = false;
+    uint8_t ldpc_tables[2560] = {};       // the same LdpcTables on the host: an AP call (ap_kernels.hpp) uploads the code in force AT THE CALL beside its patterns
     uint32_t osd_gen[91 * 6] = {};        // OsdGen (ldpc_host.hpp): a generator of the loaded code, derived with the tables while rank H = 83
     void *d_osdgen = nullptr;             // its device copy: allocated by the first cwslg_enable_ft8_osd / cwslg_enable_ft4_osd / cwslg_osd_decode, replaced by every later cwslg_set_ldpc_code
     bool osd_ready = false;               // the loaded code has rank 83: OSD may be enabled
@@ -82,6 +83,8 @@ struct SyncShared {
     void *d_encgen = nullptr;             // its device copy: made by the first cwslg_fetch_decode_reports / cwslg_fetch_ft4_decode_reports after a (re)load
     bool enc_ready = false;               // columns 91..173 of the loaded H are invertible: words can be re-encoded
     bool enc_dirty = false;               // enc_gen is newer than the device copy
+    uint32_t ap_block[8 * 6] = {};        // cwslg_set_ft8_ap: the patterns as the kernel reads them (ap_host.hpp: ApBlock); host bytes only -- every AP call uploads the block in force
+    int ap_npat = 0, ap_max_iter = 30, ap_min_nsync = 7;
 };
 
 struct SyncChannelBuffers {

@@ -423,7 +423,7 @@ int cwslg_fetch_ft8_softbits(cwslg_ctx *ctx, int ch_id, cwslg_ft8_soft *dst, int
 /* FT8 decode (row a13; PARITY UNPINNED): flooding sum-product decoding of the LDPC(174,91) code on the 174 metrics of every cwslg_ft8_soft record,
  * then the CRC-14 -- the first consumer of those metrics, on the device: per candidate 91 bits, "is a codeword", "CRC matches" and an iteration
  * count (20 bytes) instead of 704 bytes over the link and belief propagation on the host.  Structured like upstream bpdecode174_91.  Out of scope:
- * ordered-statistics decoding (a stage of its own: FT8 OSD below), a-priori passes, signal subtraction, unpacking the 77 bits into text.  De-duplication (neighbouring candidates of
+ * ordered-statistics decoding (a stage of its own: FT8 OSD below), a-priori passes (a fetch of their own: FT8 a-priori decoding below), signal subtraction, unpacking the 77 bits into text.  De-duplication (neighbouring candidates of
  * one transmission repeat one message) is not this stage's either: cwslg_fetch_decodes below hands the words of a whole group out chosen and de-duplicated.  Off by default; while it is off nothing changes (launches, buffers, upload bytes, lists, records).
  *   The code is DATA THE CALLER LOADS: the WSJT-X source is not part of this repository and its parity-check table is not reproduced here.
  *       cwslg_set_ldpc_code takes the 83 x 7 table `Nm` of the integrator's own WSJT-X tree (recalled, not checked here, as lib/ft8/ldpc_174_91_c_parity.f90), row-major: entry =
@@ -644,7 +644,7 @@ int cwslg_fetch_ft4_osd(cwslg_ctx *ctx, int ch_id, cwslg_ft4_osd *dst, int max, 
 typedef struct {
     int32_t  ch_id;
     int16_t  entry;      /* FT8: index into the candidate list; FT4: index of the sync record as cwslg_fetch_ft4_sync compacts them */
-    uint8_t  by_osd;     /* 0: word of the decode record (BP); 1: word of the OSD record */
+    uint8_t  by_osd;     /* 0: word of the decode record (BP); 1: word of the OSD record; 2 (cwslg_fetch_ft8_ap only): word of the AP record, set = its pattern */
     uint8_t  set;        /* FT4: metric set 0..2 the word came from; FT8: 0 */
     uint8_t  bits[12];   /* as cwslg_ft8_msg.bits */
     float    freq_hz;    /* FT8: candidate freq_hz; FT4: record f1_hz */
@@ -693,7 +693,7 @@ int cwslg_fetch_decodes(cwslg_ctx *ctx, int group, uint64_t *start_epoch /* in/o
  * for reports holds no device byte of it.  It writes no record, list, stamp or statistic.
  * The report uses the code IN FORCE AT THE CALL: words decoded under an earlier table are re-encoded under the new one (their first 91 bits are
  * kept; parity, tones and therefore the figures are the new code's).
- * Out of scope: unpacking to text, a-priori passes, signal subtraction, xsnr2 (FT4 reports: the next block). */
+ * Out of scope: unpacking to text, signal subtraction, xsnr2 (FT4 reports: the next block). */
 typedef struct {
     float   snr_db;      /* see above; never below -24 (FT4: -21) */
     float   xsig;        /* power at the re-encoded tones */
@@ -744,6 +744,51 @@ int cwslg_ft8_tones(cwslg_ctx *ctx, const uint8_t *bits /* [12] */, uint8_t *ton
 int cwslg_fetch_ft4_decode_reports(cwslg_ctx *ctx, uint64_t *start_epoch /* in/out */, cwslg_decode *dec, cwslg_decode_report *rep, int max,
                                    int *n, int *n_total, int *n_channels);
 int cwslg_ft4_tones(cwslg_ctx *ctx, const uint8_t *bits /* [12] */, uint8_t *tones /* [103] */);
+/* FT8 a-priori decoding (PARITY UNPINNED like the rest of the chain): the candidates that belief propagation and OSD gave up on, decoded again
+ * with some of the 91 message bits TOLD to the decoder.  Nearly every transmission a skimmer wants to spot begins with a known field; telling the
+ * decoder those bits buys sensitivity on exactly those messages (measured against this chain's own BP + OSD: DESIGN.md 4.12).  Everything it
+ * needs is on the device after a boundary -- the alternative is 704 bytes per failed candidate over the link and BP on the host.  A FETCH with a
+ * kernel inside, not a stage: no record kind, no stamp, no launch at a boundary, no field in cwslg_stats, stats.sync_launches untouched.
+ * tests/ap_ref.py restates everything below in numpy.
+ *   Patterns are DATA THE CALLER LOADS, as the parity-check table is: nothing here knows what "CQ" packs to.  A pattern is a mask and a value over
+ *       codeword bits 0..90, both packed as cwslg_ft8_msg.bits.  cwslg_set_ft8_ap(ctx, pat, n_pat 0..8 (0 clears the patterns), max_iter 1..200,
+ *       min_nsync 0..22) returns CWSLG_ERR_ARG for an argument out of range, a mask or value bit at position 91..95, or a value bit outside its
+ *       mask; the patterns in force then stay.  A mask with no bit set is allowed: it is a second plain BP pass.  The call has host effect only and
+ *       may be repeated at any time; every AP call takes the patterns (and the code) IN FORCE AT THE CALL up with its own upload.
+ *   Arithmetic per metric set llr[174]; every operation is ONE un-fused float32 operation.
+ *     1. If any llr[t] is not finite the set is NOT ATTEMPTED.
+ *     2. A = 1.01f * max_t |llr[t]| (the max is exact, the product one multiply).
+ *     3. For p = 0, 1, ... in the caller's order: llr_p[t] = (value_p[t] ? +A : -A) where mask_p[t] is set, llr[t] elsewhere.
+ *     4. The decode contract's loop (steps 1 to 8 of cwslg_ft8_msg, the same T, A(y) and early stop) runs on llr_p with max_iter, from messages +0.
+ *     5. Pattern p SUCCEEDS iff at exit nbad == 0, the CRC-14 rule holds, and cw[t] == value_p[t] on every masked t -- a word that contradicts
+ *        the hypothesis it was found under is not a find.
+ *     6. The first p that succeeds ends the set.
+ *   Record on success: bits and iters of that run, nbad = 0, crc_ok = 1, pad_ = p; nharderr = #{t < 174 : (llr[t] > 0) != cw[t]} and dmin = OSD's
+ *       distance (rule 7 of cwslg_osd_msg: the ascending-t chain from +0 over |llr[t]| of the disagreeing t), both against the ORIGINAL metrics:
+ *       dmin is the gate upstream applies to AP decodes.  Without success: zero bits, iters = the SUM of all runs' iteration counts, nbad = the
+ *       last run's, nharderr = -1, crc_ok = 0, pad_ = 0xff, dmin = +0.  Not attempted: the decode record's "not attempted" bytes, pad_ = 0xff,
+ *       dmin = +0.
+ * cwslg_ap_decode runs the kernel on n >= 0 caller-supplied sets (host memory) with no nsync gate, synchronously: the twin of cwslg_ldpc_decode
+ * and cwslg_osd_decode.  CWSLG_ERR_ARG without a loaded code or with no pattern set.
+ * cwslg_fetch_ft8_ap is cwslg_fetch_decodes' contract for CWSLG_GROUP_FT8, points 1 to 7 above, with these differences.  Which channels take
+ * part, and whether a channel's OSD records are used, is decided exactly as there (points 2 and 3).  Entry q of a channel is ATTEMPTED iff its
+ * decode record was attempted (iters >= 0) and has crc_ok == 0; the OSD records are not used, or its OSD record has crc_ok == 0; its soft record
+ * has nsync >= min_nsync; and rule 1 holds.  An entry's word is its AP record's, if crc_ok; the all-zero word is dropped; equal words of one
+ * channel fold into one cwslg_decode ranked by (nharderr, entry), with ndup; the order is ch_id, then entry -- the harvest kernel's existing
+ * modes, run on the AP records.  Each emitted record has by_osd = 2, set = the pattern index and dmin = the AP record's.  Words that another
+ * entry of the channel already decoded by BP or OSD are NOT removed here: merge on the host by bits[12] per ch_id, BP / OSD winning
+ * (mergeApDecodes in cwsl_gpu_shim.hpp, merge_ap_decodes in api.py).  CWSLG_ERR_ARG with no pattern set or no code loaded.  Execution, one
+ * ticket and one serialised call of the group: descriptors, pattern block and tables go up in one copy, the a-priori decode runs (a mode of ldpc_decode_kernel: one wave
+ * per candidate, the count read on the device), the three harvest launches run on its records, ONE further launch (another mode of that kernel)
+ * annotates the emitted records, ONE copy down, one synchronise.  Staging: per taking-part channel max_cand x (20 + 4) bytes; it belongs to the
+ * group, is allocated at the first call, grows, and is freed by cwslg_destroy: a context that never calls holds no byte of it.
+ * Out of scope: FT4 AP, AP words inside cwslg_fetch_decodes itself, packing call signs into patterns, unpacking to text, signal subtraction, OSD
+ * on AP-modified metrics. */
+typedef struct { uint8_t mask[12]; uint8_t value[12]; } cwslg_ap_pattern;   /* codeword bits 0..90, packed as cwslg_ft8_msg.bits */
+typedef struct { cwslg_ft8_msg msg; float dmin; } cwslg_ap_msg;             /* 24 bytes; msg.pad_ = pattern index, 0xff: none */
+int cwslg_set_ft8_ap(cwslg_ctx *ctx, const cwslg_ap_pattern *pat, int n_pat, int max_iter, int min_nsync);
+int cwslg_fetch_ft8_ap(cwslg_ctx *ctx, uint64_t *start_epoch /* in/out */, cwslg_decode *dst, int max, int *n, int *n_total, int *n_channels);
+int cwslg_ap_decode(cwslg_ctx *ctx, const float *llr /* [n][174] */, int n, cwslg_ap_msg *out);
 int cwslg_fetch_slot(cwslg_ctx *ctx, int ch_id, int16_t *frame, size_t cap, void *list, size_t list_bytes,
                      cwslg_ft4_sync *ft4, int max_ft4, cwslg_slot_result *out);
 int cwslg_set_ft4_syncmin(cwslg_ctx *ctx, float syncmin);

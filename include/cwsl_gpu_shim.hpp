@@ -26,6 +26,8 @@
 #include <string>
 #include <vector>
 #include <array>
+#include <algorithm>
+#include <cstring>
 #include <complex>
 
 #include "cwsl_gpu.h"
@@ -42,6 +44,25 @@ inline void check(cwslg_ctx *c, int rc)
         throw std::invalid_argument(cwslg_strerror(rc));
     if (rc == CWSLG_ERR_MODE) throw std::runtime_error(msg);          // CWSL_DIGI.hpp:111
     throw std::runtime_error("libcwslgpu: " + msg);
+}
+
+// What cwslg_fetch_ft8_ap leaves to the host: `decodes` (cwslg_fetch_decodes) followed by those records of `ap` (cwslg_fetch_ft8_ap, the same
+// epoch) whose bits[12] no record of `decodes` with the same ch_id carries -- BP / OSD win -- in ascending (ch_id, entry, by_osd).
+inline std::vector<cwslg_decode> mergeApDecodes(const std::vector<cwslg_decode> &decodes, const std::vector<cwslg_decode> &ap)
+{
+    std::vector<cwslg_decode> out(decodes);
+    for (const cwslg_decode &a : ap) {
+        bool have = false;
+        for (const cwslg_decode &d : decodes)
+            if (d.ch_id == a.ch_id && std::memcmp(d.bits, a.bits, sizeof(a.bits)) == 0) { have = true; break; }
+        if (!have) out.push_back(a);
+    }
+    std::stable_sort(out.begin(), out.end(), [](const cwslg_decode &x, const cwslg_decode &y) {
+        if (x.ch_id != y.ch_id) return x.ch_id < y.ch_id;
+        if (x.entry != y.entry) return x.entry < y.entry;
+        return x.by_osd < y.by_osd;
+    });
+    return out;
 }
 
 // Which of a cwslg_ft4_msg's three sets a consumer takes: upstream tries the metric sets in order and stops at the first success, which is the
@@ -141,6 +162,33 @@ public:
         check(c_, rc);
         out.resize(n);
         reports.resize(n);
+        return total;
+    }
+    // FT8 a-priori decoding: the patterns are the caller's data (cwslg_set_ft8_ap validates them: at most 8, none clears them), tried in this
+    // order on the candidates BP and OSD gave up on.  apDecode runs the kernel on caller-supplied metrics; fetchFt8Ap is fetchDecodes' shape for
+    // the a-priori words of the FT8 group (by_osd = 2, set = the pattern, dmin = OSD's distance of the word): words BP / OSD already have are
+    // not removed there -- mergeApDecodes below.
+    void setFt8Ap(const cwslg_ap_pattern *patterns, int nPatterns, int maxIter = 30, int minNsync = 7)
+    {
+        check(c_, cwslg_set_ft8_ap(c_, patterns, nPatterns, maxIter, minNsync));
+    }
+    void setFt8Ap(const std::vector<cwslg_ap_pattern> &patterns, int maxIter = 30, int minNsync = 7)
+    {
+        setFt8Ap(patterns.empty() ? nullptr : patterns.data(), static_cast<int>(patterns.size()), maxIter, minNsync);
+    }
+    void apDecode(const float *llr, int n, std::vector<cwslg_ap_msg> &out)
+    {
+        out.resize(n);
+        check(c_, cwslg_ap_decode(c_, llr, n, out.data()));
+    }
+    int fetchFt8Ap(std::vector<cwslg_decode> &out, std::uint64_t &startEpoch, int max = 4096, int *nChannels = nullptr)
+    {
+        out.resize(max > 0 ? max : 0);
+        int n = 0, total = 0;
+        const int rc = cwslg_fetch_ft8_ap(c_, &startEpoch, out.data(), static_cast<int>(out.size()), &n, &total, nChannels);
+        if (rc == CWSLG_ERR_NO_FRAME) { out.clear(); return 0; }
+        check(c_, rc);
+        out.resize(n);
         return total;
     }
     // The 79 channel tones of a 91-bit word (cwslg_decode.bits) under the code in force: the reports' re-encoder on its own, host work only
