@@ -162,8 +162,8 @@ assert AP_PATTERN_DTYPE.itemsize == 24 and AP_MSG_DTYPE.itemsize == 24
 
 
 def merge_ap_decodes(decodes, ap):
-    """What cwslg_fetch_ft8_ap leaves to the host: the records of fetch_decodes followed by those records of fetch_ft8_ap (both DECODE_DTYPE, of
-    one epoch) whose bits[12] no BP / OSD record of the same ch_id carries -- BP / OSD win -- in ascending (ch_id, entry), BP / OSD first
+    """What cwslg_fetch_ft8_ap (and cwslg_fetch_ft4_ap) leaves to the host: the records of fetch_decodes followed by those records of fetch_ft8_ap /
+    fetch_ft4_ap (both DECODE_DTYPE, of one epoch and group) whose bits[12] no BP / OSD record of the same ch_id carries -- BP / OSD win -- in ascending (ch_id, entry), BP / OSD first
     where both name one entry's channel position."""
     decodes, ap = np.asarray(decodes, DECODE_DTYPE), np.asarray(ap, DECODE_DTYPE)
     have = {(int(d["ch_id"]), d["bits"].tobytes()) for d in decodes}
@@ -171,6 +171,13 @@ def merge_ap_decodes(decodes, ap):
     out = np.concatenate([decodes, ap[keep]])
     order = sorted(range(len(out)), key=lambda i: (int(out["ch_id"][i]), int(out["entry"][i]), int(out["by_osd"][i])))
     return out[order]
+
+
+def ap_set_split(set_byte):
+    """The `set` byte of an FT4 a-priori record (fetch_ft4_ap: by_osd = 2) -> (metric set, pattern index): set & 3, set >> 2.  Scalars or arrays."""
+    v = np.asarray(set_byte).astype(np.int64)
+    s, p = v & 3, v >> 2
+    return (int(s), int(p)) if v.ndim == 0 else (s, p)
 
 
 class DecodeReport(C.Structure):
@@ -232,7 +239,7 @@ ABI_SYMBOLS = [
     "cwslg_enable_ft8_osd", "cwslg_fetch_ft8_osd", "cwslg_osd_decode", "cwslg_enable_ft4_decode", "cwslg_fetch_ft4_decode",
     "cwslg_enable_ft4_osd", "cwslg_fetch_ft4_osd", "cwslg_fetch_decodes",
     "cwslg_fetch_decode_reports", "cwslg_ft8_tones", "cwslg_fetch_ft4_decode_reports", "cwslg_ft4_tones",
-    "cwslg_set_ft8_ap", "cwslg_fetch_ft8_ap", "cwslg_ap_decode",
+    "cwslg_set_ft8_ap", "cwslg_fetch_ft8_ap", "cwslg_ap_decode", "cwslg_set_ft4_ap", "cwslg_fetch_ft4_ap",
     "cwslg_set_timing", "cwslg_demod_kernel_name", "cwslg_stream", "cwslg_channel_constants", "cwslg_phasor_checkpoint_stride", "cwslg_channel_phasor_checkpoints",
     "cwslg_slot_clock_next", "cwslg_pool_sizing", "cwslg_find_band", "cwslg_parse_decode_line",
     "cwslg_decoder_block_bytes", "cwslg_decoder_block_field", "cwslg_fill_decoder_block", "cwslg_decoder_route", "cwslg_decoder_command",
@@ -341,6 +348,8 @@ def load_library(build_if_missing=True):
     L.cwslg_set_ft8_ap.argtypes = [vp, vp, i32, i32, i32]
     L.cwslg_fetch_ft8_ap.argtypes = [vp, C.POINTER(u64), vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     L.cwslg_ap_decode.argtypes = [vp, vp, i32, vp]
+    L.cwslg_set_ft4_ap.argtypes = [vp, vp, i32, i32, i32, i32]
+    L.cwslg_fetch_ft4_ap.argtypes = [vp, C.POINTER(u64), vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     L.cwslg_sync_debug_fetch.argtypes = [vp, i32, i32, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(i32)]
     L.cwslg_get_stats.argtypes = [vp, C.POINTER(Stats)]
     L.cwslg_reset_stats.argtypes = [vp]
@@ -894,9 +903,8 @@ class Context:
         self._chk(rc)
         return dec[:n.value].copy(), rep[:n.value].copy(), t0.value, n_total.value, n_ch.value
 
-    def set_ft8_ap(self, patterns, max_iter=30, min_nsync=7):
-        """cwslg_set_ft8_ap: the a-priori patterns (AP_PATTERN_DTYPE array, or a sequence of (mask[12], value[12]) byte pairs; at most 8, none
-        clears them), tried in this order by ap_decode and fetch_ft8_ap.  Host effect only."""
+    @staticmethod
+    def _ap_patterns(patterns):
         pat = np.zeros(len(patterns), AP_PATTERN_DTYPE)
         if isinstance(patterns, np.ndarray) and patterns.dtype == AP_PATTERN_DTYPE:
             pat[:] = patterns
@@ -904,7 +912,32 @@ class Context:
             for i, (m, v) in enumerate(patterns):
                 pat["mask"][i] = np.frombuffer(bytes(m), np.uint8)
                 pat["value"][i] = np.frombuffer(bytes(v), np.uint8)
+        return pat
+
+    def set_ft8_ap(self, patterns, max_iter=30, min_nsync=7):
+        """cwslg_set_ft8_ap: the a-priori patterns (AP_PATTERN_DTYPE array, or a sequence of (mask[12], value[12]) byte pairs; at most 8, none
+        clears them), tried in this order by ap_decode and fetch_ft8_ap.  Host effect only."""
+        pat = self._ap_patterns(patterns)
         self._chk(self.L.cwslg_set_ft8_ap(self.h, pat.ctypes.data if len(pat) else None, len(pat), int(max_iter), int(min_nsync)))
+
+    def set_ft4_ap(self, patterns, max_iter=30, min_nsync=8, min_nqual=20):
+        """cwslg_set_ft4_ap: the FT4 a-priori patterns, a state of their own beside set_ft8_ap's (FT4's message bits are scrambled on the air: the
+        patterns hold the scrambled values).  The same forms of `patterns`; tried in this order by fetch_ft4_ap.  Host effect only."""
+        pat = self._ap_patterns(patterns)
+        self._chk(self.L.cwslg_set_ft4_ap(self.h, pat.ctypes.data if len(pat) else None, len(pat), int(max_iter), int(min_nsync), int(min_nqual)))
+
+    def fetch_ft4_ap(self, start_epoch=0, max=4096):
+        """cwslg_fetch_ft4_ap: the a-priori words of the FT4 group -- the sync records BP and OSD gave up on in every set, each set decoded under the
+        patterns of set_ft4_ap, the smallest set with a find chosen, de-duplicated like fetch_decodes.  -> None if no channel takes part, else
+        (records, start_epoch, n_total, n_channels): records DECODE_DTYPE with by_osd = 2, set = metric set | pattern << 2 (ap_set_split), dmin =
+        OSD's distance of the word.  Words BP / OSD already have are not removed: merge_ap_decodes."""
+        buf = np.zeros(int(max) if int(max) > 1 else 1, DECODE_DTYPE)
+        t0, n, n_total, n_ch = C.c_uint64(int(start_epoch)), C.c_int(), C.c_int(), C.c_int()
+        rc = self.L.cwslg_fetch_ft4_ap(self.h, C.byref(t0), buf.ctypes.data if int(max) > 0 else None, int(max), C.byref(n), C.byref(n_total), C.byref(n_ch))
+        if rc == ERR_NO_FRAME:
+            return None
+        self._chk(rc)
+        return buf[:n.value].copy(), t0.value, n_total.value, n_ch.value
 
     def ap_decode(self, llr):
         """The a-priori kernel on caller-supplied metrics, llr float32[n, 174] (n >= 0), no nsync gate; synchronous.  -> AP_MSG_DTYPE array [n]."""

@@ -1,4 +1,4 @@
-// ap_kernels.hpp -- FT8 a-priori decoding on gfx950: the candidates belief propagation and OSD gave up on are decoded again with some of the
+// ap_kernels.hpp -- FT8 and FT4 a-priori decoding on gfx950: the candidates (FT4: sync records) belief propagation and OSD gave up on are decoded again with some of the
 // 91 message bits TOLD to the decoder -- a caller's patterns (mask + value, e.g. the bits of "CQ"), tried in the caller's order -- and the first
 // pattern under which the loop of the decode contract reaches a CRC-passing codeword that agrees with the pattern is the find.
 //
@@ -6,7 +6,7 @@
 // tests/ap_ref.py restates in numpy, BIT FOR BIT.  The patterns are DATA the caller loads (cwslg_set_ft8_ap): nothing here knows what a message
 // packs to.  This translation unit is built -ffp-contract=off: every product and sum below is one float32 operation.
 //
-// This is a FETCH with a kernel inside, not a stage (cwslg_fetch_ft8_ap): it reads the records the chain has left on the device and writes only
+// This is a FETCH with a kernel inside, not a stage (cwslg_fetch_ft8_ap, cwslg_fetch_ft4_ap): it reads the records the chain has left on the device and writes only
 // the group's staging.  The product library keeps one kernel per job and a test holds its count, so the a-priori work has no symbol of its own:
 // it is two further modes of ldpc_decode_kernel -- whose loop, LDS image and launch shape it shares -- behind one launch-uniform branch
 // (ApArgs::mode; ldpc_kernels.hpp), as the FT4 report is a mode of ft4_softbits_kernel:
@@ -19,11 +19,19 @@
 //                left), not a tree.  No cross-wave traffic, no workgroup barrier, every exit wave-uniform.  So that the hosting kernel keeps its
 //                registers (and the decode launch its occupancy), nothing but the graph stays live across a run: the original metrics of bits l and
 //                l + 64 are read again per pattern, A and the pattern words are scalars.
-//                Two ways of finding llr and out: desc != nullptr, candidate q of channel blockIdx.y behind the gate of the contract (its decode
-//                record attempted without crc_ok, its OSD record -- where used -- without crc_ok, nsync >= min_nsync), 20-byte record to
-//                ap[q] and dmin to dmin[q];  desc == nullptr, cwslg_ap_decode: n_flat sets from llr_flat, no gate, 24-byte cwslg_ap_msg.
+//                Three ways of finding llr and out, chosen by launch-uniform fields of ApArgs: desc != nullptr, candidate q of channel blockIdx.y
+//                behind the gate of the contract (its decode record attempted without crc_ok, its OSD record -- where used -- without crc_ok,
+//                nsync >= min_nsync), 20-byte record to ap[q] and dmin to dmin[q];  desc == nullptr, cwslg_ap_decode: n_flat sets from llr_flat,
+//                no gate, 24-byte cwslg_ap_msg;  desc != nullptr and ft4 (cwslg_fetch_ft4_ap), the FT4 decode's addressing: one wave per (record
+//                slot, metric set), grid (ceil(9 cap_max / 4), taking-part channels), wave q: slot = q / 3, s = q % 3, cand = slot / 3,
+//                r = slot % 3, gone if q >= 9 cap, cand >= min(*cnt, cap) or r >= nrec[cand]; the gate is PER RECORD -- the three crc_ok bytes of
+//                the slot's decode record and, where used, of its OSD record, nsync and nqual of its Ft4SoftRec -- and per set iters >= 0;
+//                metrics llr[s] of the slot's soft record, record to set[s] of slot's Ft4MsgRec in the staging (= record q), dmin to dmin[q].
+//                All of that addressing is scalar (q goes through readfirstlane); everything behind it is the same text.
 //   AP_ANNOTATE  one thread per record decode_harvest_kernel has emitted from the AP records: the record's channel through `offsets` (as the
-//                report mode finds it), then by_osd = 2, set = the pattern index, dmin = the AP record's.
+//                report mode finds it), then by_osd = 2, set = the pattern index, dmin = the AP record's.  FT4: the metric set s from the set
+//                byte the harvest wrote, the entry's slot by a serial walk over nrec (entry e is slot 3 k + (e - prefix(k)), prefix the running
+//                sum of min(max(nrec[k], 0), 3)), then set = s | pattern << 2 and dmin[3 slot + s].
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -40,13 +48,14 @@ static_assert(sizeof(ApMsgRec) == 24, "cwslg_ap_msg is 24 bytes");
 // One channel that takes part, built by the host under the context mutex (same index as the call's HarvestDesc array).
 struct alignas(16) ApDesc {
     const int *cnt;          // the list's count
-    const void *soft;        // Ft8SoftRec[cap]
-    const void *msg;         // Ft8MsgRec[cap]
-    const void *osd;         // OsdRec[cap]; null: the OSD records are not used
-    void *ap;                // out: Ft8MsgRec[cap], what the harvest reads as the channel's decode records
-    float *dmin;             // out: [cap]
+    const void *soft;        // Ft8SoftRec[cap]; FT4: Ft4SoftRec[cap][3], the slot layout
+    const void *msg;         // Ft8MsgRec[cap]; FT4: Ft4MsgRec[cap][3]
+    const void *osd;         // OsdRec[cap]; FT4: Ft4OsdRec[cap][3]; null: the OSD records are not used
+    void *ap;                // out: Ft8MsgRec[cap] (FT4: Ft4MsgRec[cap][3]), what the harvest reads as the channel's decode records
+    float *dmin;             // out: [cap]; FT4: [cap][3][3], dmin[3 slot + s]
+    const int *nrec;         // FT4: records per candidate, [cap]; FT8: null
     int cap;                 // the list limit the arrays were sized for
-    int pad_[3];
+    int pad_;
 };
 static_assert(sizeof(ApDesc) == 64, "descriptor layout");
 
@@ -75,14 +84,31 @@ __device__ __forceinline__ void ap_annotate(const ApArgs &ap)
     const CWSLG_GLOBAL ApDesc *d = as_global(reinterpret_cast<const ApDesc *>(ap.desc)) + lo_c;
     CWSLG_GLOBAL unsigned *rec = g_out + HARVEST_HEAD_WORDS + (size_t)p * HARVEST_REC_WORDS;
     const unsigned entry = rec[1] & 0xffffu;                   // (< cap: the harvest walked min(count, cap) entries)
+    if (ap.ft4) {
+        // FT4: the metric set from the byte the harvest wrote; the entry's slot by the harvest's own walk -- slot 3 k + r exists iff r < nrec[k],
+        // entries number the existing slots in ascending order.  (The entry exists, so the walk ends inside the list.)
+        const unsigned s = rec[1] >> 24 & 3u;
+        const CWSLG_GLOBAL int *g_nrec = as_global(d->nrec);
+        const int ncand = max(0, min(*as_global(d->cnt), d->cap));
+        unsigned prefix = 0u, slot = 0u;
+        for (int k = 0; k < ncand; ++k) {
+            const unsigned nr = (unsigned)min(max(g_nrec[k], 0), 3);
+            if (entry < prefix + nr) { slot = 3u * (unsigned)k + (entry - prefix); break; }
+            prefix += nr;
+        }
+        const unsigned w4 = as_global(reinterpret_cast<const unsigned *>(d->ap))[(size_t)slot * 15u + 5u * s + 4u];
+        rec[1] = entry | 2u << 16 | (s | (w4 >> 24) << 2) << 24;
+        rec[8] = as_global(reinterpret_cast<const unsigned *>(d->dmin))[3u * slot + s];
+        return;
+    }
     const unsigned w4 = as_global(reinterpret_cast<const unsigned *>(d->ap))[(size_t)entry * 5u + 4u];      // nharderr | crc_ok << 16 | pad_ << 24
     rec[1] = entry | 2u << 16 | (w4 >> 24) << 24;
     rec[8] = as_global(reinterpret_cast<const unsigned *>(d->dmin))[entry];
 }
 
 // (declared in ldpc_kernels.hpp, in front of the kernel that calls it; s_v, s_z: the calling wave's LDS image)
-__device__ __forceinline__ void ap_modes(const ApArgs &ap, const float *llr_flat, int n_flat, int max_iter, int min_nsync, const LdpcTables *tables,
-                                         float *s_v, float *s_z)
+__device__ __forceinline__ void ap_modes(const ApArgs &ap, const float *llr_flat, int n_flat, int max_iter, int min_nsync, int min_nqual,
+                                         const LdpcTables *tables, float *s_v, float *s_z)
 {
     if (ap.mode == AP_ANNOTATE) {
         ap_annotate(ap);
@@ -93,7 +119,27 @@ __device__ __forceinline__ void ap_modes(const ApArgs &ap, const float *llr_flat
     const CWSLG_GLOBAL float *llr;
     CWSLG_GLOBAL uint32_t *ow, *od;                            // the 20-byte record, the dmin word
     bool attempt = true;
-    if (ap.desc) {
+    if (ap.desc && ap.ft4) {
+        // FT4: the decode's third addressing and its exits; wave q is set s of record slot q / 3, all of it scalar
+        const CWSLG_GLOBAL ApDesc *d = as_global(reinterpret_cast<const ApDesc *>(ap.desc)) + blockIdx.y;
+        const int qs = __builtin_amdgcn_readfirstlane(q), cap = d->cap;
+        if (qs >= 9 * cap) return;                             // wave-uniform, all three
+        const int slot = qs / 3, s = qs - 3 * slot, cand = slot / 3, r = slot - 3 * cand;
+        if (cand >= min(*as_global(d->cnt), cap)) return;
+        if (r >= as_global(d->nrec)[cand]) return;
+        const CWSLG_GLOBAL Ft4SoftRec *rec = as_global(reinterpret_cast<const Ft4SoftRec *>(d->soft)) + slot;
+        const CWSLG_GLOBAL uint32_t *m = reinterpret_cast<const CWSLG_GLOBAL uint32_t *>(as_global(reinterpret_cast<const Ft4MsgRec *>(d->msg)) + slot);
+        llr = rec->llr[s];
+        ow = reinterpret_cast<CWSLG_GLOBAL uint32_t *>(as_global_rw(reinterpret_cast<Ft8MsgRec *>(d->ap)) + qs);     // set s of slot q / 3
+        od = reinterpret_cast<CWSLG_GLOBAL uint32_t *>(as_global_rw(d->dmin) + qs);                                  // dmin[3 slot + s]
+        // the record's gate: no set with BP crc_ok (word 4 of a set: nharderr | crc_ok << 16 | pad_ << 24), nor -- where used -- with OSD crc_ok
+        // (word 5 of a set: crc_ok | how << 8 | flip << 16); this set attempted by the decode (word 3: iters | nbad << 16)
+        attempt = (int16_t)(m[5 * s + 3] & 0xffffu) >= 0 && ((m[4] | m[9] | m[14]) >> 16 & 0xffu) == 0u && rec->nsync >= min_nsync && rec->nqual >= min_nqual;
+        if (attempt && d->osd != nullptr) {
+            const CWSLG_GLOBAL uint32_t *o = reinterpret_cast<const CWSLG_GLOBAL uint32_t *>(as_global(reinterpret_cast<const Ft4OsdRec *>(d->osd)) + slot);
+            attempt = ((o[5] | o[11] | o[17]) & 0xffu) == 0u;
+        }
+    } else if (ap.desc) {
         const CWSLG_GLOBAL ApDesc *d = as_global(reinterpret_cast<const ApDesc *>(ap.desc)) + blockIdx.y;
         const int ncand = min(*as_global(d->cnt), d->cap);
         if (q >= ncand) return;                                // wave-uniform
@@ -188,20 +234,22 @@ __device__ __forceinline__ void ap_modes(const ApArgs &ap, const float *llr_flat
 }
 
 // The launches of the a-priori modes: ldpc_decode_kernel with the decode's own arguments null / 0.  The caller asks hipGetLastError.
-inline void ap_launch(hipStream_t s, dim3 grid, const float *llr, int n_flat, int max_iter, int min_nsync, const void *tables, const ApArgs &ap)
+inline void ap_launch(hipStream_t s, dim3 grid, const float *llr, int n_flat, int max_iter, int min_nsync, const void *tables, const ApArgs &ap,
+                      int min_nqual = 0)
 {
     hipLaunchKernelGGL(ldpc_decode_kernel, grid, dim3(64 * LDPC_WAVES), 0, s, (const SyncWork *)nullptr, (Ft8SoftRec *const *)nullptr, (Ft8MsgRec *const *)nullptr,
                        llr, (Ft8MsgRec *)nullptr, n_flat, 0, max_iter, min_nsync, (const LdpcTables *)tables, (const Ft4Work *)nullptr,
-                       (Ft4SoftRec *const *)nullptr, (Ft4MsgRec *const *)nullptr, 0, ap);
+                       (Ft4SoftRec *const *)nullptr, (Ft4MsgRec *const *)nullptr, min_nqual, ap);
 }
-//   AP_DECODE on the n_chan channels of d_desc (cap_max: the largest cap among them)
+//   AP_DECODE on the n_chan channels of d_desc (cap_max: the largest cap among them); ft4: a wave per (record slot, metric set), 9 per candidate
 inline void ap_launch_chain(hipStream_t s, const ApDesc *d_desc, int n_chan, int cap_max, int max_iter, int min_nsync, const void *tables,
-                            const void *pats, int n_pat)
+                            const void *pats, int n_pat, bool ft4 = false, int min_nqual = 0)
 {
     if (n_chan <= 0 || cap_max <= 0) return;
     ApArgs ap{};
-    ap.mode = AP_DECODE; ap.n_pat = n_pat; ap.desc = d_desc; ap.pats = pats; ap.n_chan = n_chan;
-    ap_launch(s, dim3((unsigned)((cap_max + LDPC_WAVES - 1) / LDPC_WAVES), (unsigned)n_chan), nullptr, 0, max_iter, min_nsync, tables, ap);
+    ap.mode = AP_DECODE; ap.n_pat = n_pat; ap.desc = d_desc; ap.pats = pats; ap.n_chan = n_chan; ap.ft4 = ft4 ? 1 : 0;
+    const int waves = ft4 ? 9 * cap_max : cap_max;
+    ap_launch(s, dim3((unsigned)((waves + LDPC_WAVES - 1) / LDPC_WAVES), (unsigned)n_chan), nullptr, 0, max_iter, min_nsync, tables, ap, min_nqual);
 }
 //   AP_DECODE flat: n sets of 174 metrics, no gate
 inline void ap_launch_flat(hipStream_t s, const void *tables, const void *pats, int n_pat, const float *llr, ApMsgRec *out, int n, int max_iter)
@@ -212,11 +260,11 @@ inline void ap_launch_flat(hipStream_t s, const void *tables, const void *pats, 
     ap_launch(s, dim3((unsigned)((n + LDPC_WAVES - 1) / LDPC_WAVES), 1), llr, n, max_iter, 0, tables, ap);
 }
 //   AP_ANNOTATE behind harvest_launch on the same stream and blocks: a thread per record that emit may have written
-inline void ap_launch_annotate(hipStream_t s, const ApDesc *d_desc, const unsigned *d_offsets, unsigned *d_out, int n_chan, int lim)
+inline void ap_launch_annotate(hipStream_t s, const ApDesc *d_desc, const unsigned *d_offsets, unsigned *d_out, int n_chan, int lim, bool ft4 = false)
 {
     if (lim <= 0) return;
     ApArgs ap{};
-    ap.mode = AP_ANNOTATE; ap.desc = d_desc; ap.offsets = d_offsets; ap.out = d_out; ap.n_chan = n_chan; ap.max_out = lim;
+    ap.mode = AP_ANNOTATE; ap.desc = d_desc; ap.offsets = d_offsets; ap.out = d_out; ap.n_chan = n_chan; ap.max_out = lim; ap.ft4 = ft4 ? 1 : 0;
     ap_launch(s, dim3((unsigned)((lim + 64 * LDPC_WAVES - 1) / (64 * LDPC_WAVES))), nullptr, 0, 0, 0, nullptr, ap);
 }
 

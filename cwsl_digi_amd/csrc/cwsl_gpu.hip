@@ -226,8 +226,8 @@ struct HarvestStage {
     std::mutex mu;
     char *h = nullptr, *d = nullptr;
     size_t h_bytes = 0, d_bytes = 0;
-    // cwslg_fetch_ft8_ap (ap_kernels.hpp; the FT8 group's stage only): per taking-part channel cap x (20 + 4) bytes of AP records and their dmin,
-    // allocated by the first such call, grown on demand, freed by cwslg_destroy
+    // cwslg_fetch_ft8_ap / cwslg_fetch_ft4_ap (ap_kernels.hpp), each in its group's stage: per taking-part channel cap x (20 + 4) bytes of AP
+    // records and their dmin (FT4: 3 cap x (60 + 12)), allocated by the first such call, grown on demand, freed by cwslg_destroy
     char *d_ap = nullptr;
     size_t ap_bytes = 0;
 };

@@ -169,10 +169,11 @@ struct ApArgs {
     const unsigned *offsets;           // AP_ANNOTATE: the harvest's offsets and output block
     unsigned *out;
     int n_chan, max_out;
+    int ft4;                           // desc names FT4 channels: the slot layout, three sets per record (ap_kernels.hpp)
 };
 constexpr int AP_OFF = 0, AP_DECODE = 1, AP_ANNOTATE = 2;
-__device__ __forceinline__ void ap_modes(const ApArgs &ap, const float *llr_flat, int n_flat, int max_iter, int min_nsync, const LdpcTables *tables,
-                                         float *s_v, float *s_z);
+__device__ __forceinline__ void ap_modes(const ApArgs &ap, const float *llr_flat, int n_flat, int max_iter, int min_nsync, int min_nqual,
+                                         const LdpcTables *tables, float *s_v, float *s_z);
 
 __global__ __launch_bounds__(64 * LDPC_WAVES) void ldpc_decode_kernel(const SyncWork *__restrict__ works, Ft8SoftRec *const *__restrict__ soft,
                                                                       Ft8MsgRec *const *__restrict__ msg, const float *__restrict__ llr_flat,
@@ -184,7 +185,7 @@ __global__ __launch_bounds__(64 * LDPC_WAVES) void ldpc_decode_kernel(const Sync
     __shared__ __attribute__((aligned(16))) float s_vall[LDPC_WAVES][LDPC_VSIZE];
     __shared__ __attribute__((aligned(16))) float s_zall[LDPC_WAVES][192];
     if (ap.mode != AP_OFF) {                                   // uniform over the launch
-        ap_modes(ap, llr_flat, n_flat, max_iter, min_nsync, tables, s_vall[threadIdx.x >> 6], s_zall[threadIdx.x >> 6]);
+        ap_modes(ap, llr_flat, n_flat, max_iter, min_nsync, min_nqual, tables, s_vall[threadIdx.x >> 6], s_zall[threadIdx.x >> 6]);
         return;
     }
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;

@@ -840,12 +840,13 @@ int cwslg_osd_decode(cwslg_ctx *c, const float *llr, int n, int order, cwslg_osd
 
 // FT8 a-priori decoding (ap_kernels.hpp).  The patterns are the caller's data: validated and packed on the host (ap_host.hpp), host bytes only --
 // every AP call takes the block in force at the call up with its own upload, so nothing queued ever reads a block that a later set replaces.
-int cwslg_set_ft8_ap(cwslg_ctx *c, const cwslg_ap_pattern *pat, int n_pat, int max_iter, int min_nsync)
+static int set_ap_impl(cwslg_ctx *c, const cwslg_ap_pattern *pat, int n_pat, int max_iter, int min_nsync, int min_nqual, bool ft4)
 {
     static_assert(sizeof(cwslg_ap_pattern) == sizeof(ApPattern), "pattern layout");
     if (!c) return CWSLG_ERR_ARG;
     std::lock_guard<std::mutex> g(c->mu);
-    if (max_iter < 1 || max_iter > 200 || min_nsync < 0 || min_nsync > 22) return fail(c, CWSLG_ERR_ARG, "FT8 AP parameters out of range");
+    if (max_iter < 1 || max_iter > 200 || min_nsync < 0 || min_nsync > (ft4 ? 17 : 22) || min_nqual < 0 || min_nqual > 33)
+        return fail(c, CWSLG_ERR_ARG, "%s AP parameters out of range", ft4 ? "FT4" : "FT8");
     ApBlock b;
     const int why = ap_pack(reinterpret_cast<const ApPattern *>(pat), n_pat, &b);
     if (why) {
@@ -853,10 +854,26 @@ int cwslg_set_ft8_ap(cwslg_ctx *c, const cwslg_ap_pattern *pat, int n_pat, int m
         return fail(c, CWSLG_ERR_ARG, "AP patterns rejected: %s", reason[why]);
     }
     SyncShared &s = c->sync_shared;
-    static_assert(sizeof(s.ap_block) == sizeof(ApBlock), "pattern block");
-    std::memcpy(s.ap_block, &b, sizeof(ApBlock));
-    s.ap_npat = n_pat; s.ap_max_iter = max_iter; s.ap_min_nsync = min_nsync;
+    static_assert(sizeof(s.ap_block) == sizeof(ApBlock) && sizeof(s.ap4_block) == sizeof(ApBlock), "pattern block");
+    if (ft4) {
+        std::memcpy(s.ap4_block, &b, sizeof(ApBlock));
+        s.ap4_npat = n_pat; s.ap4_max_iter = max_iter; s.ap4_min_nsync = min_nsync; s.ap4_min_nqual = min_nqual;
+    } else {
+        std::memcpy(s.ap_block, &b, sizeof(ApBlock));
+        s.ap_npat = n_pat; s.ap_max_iter = max_iter; s.ap_min_nsync = min_nsync;
+    }
     return CWSLG_OK;
+}
+
+int cwslg_set_ft8_ap(cwslg_ctx *c, const cwslg_ap_pattern *pat, int n_pat, int max_iter, int min_nsync)
+{
+    return set_ap_impl(c, pat, n_pat, max_iter, min_nsync, 0, false);
+}
+
+// The FT4 patterns: a state of their own beside the FT8 one (the same validation, cwslg_enable_ft4_decode's ranges for the two minima).
+int cwslg_set_ft4_ap(cwslg_ctx *c, const cwslg_ap_pattern *pat, int n_pat, int max_iter, int min_nsync, int min_nqual)
+{
+    return set_ap_impl(c, pat, n_pat, max_iter, min_nsync, min_nqual, true);
 }
 
 // The a-priori decode (ap_kernels.hpp: a mode of ldpc_decode_kernel) on n sets of 174 metrics from host memory, no gate; synchronous (temporary device buffers, the context's stream).  The
@@ -982,7 +999,7 @@ int cwslg_fetch_ft4_osd(cwslg_ctx *c, int ch_id, cwslg_ft4_osd *dst, int max, in
 // records_queued queues it only behind REC_SOFT4 and REC_FT4SYNC, i.e. with ft4_coherent on in the configuration of that boundary -- the same
 // switch under which sync_launch runs ft4_dft567 / ft4_fft64_unpack on the channel's Ft4Work (cx = d_cx).  d_cx therefore holds THAT frame's
 // spectrum, and the sync records read here are that boundary's too: no path hands a stale spectrum to the report.
-// a-priori (cwslg_fetch_ft8_ap, FT8 only; ap_kernels.hpp): an ApDesc per channel, the pattern block and the tables of the code in force go up
+// a-priori (cwslg_fetch_ft8_ap, cwslg_fetch_ft4_ap; ap_kernels.hpp): an ApDesc per channel, the pattern block and the tables of the code in force go up
 // behind the HarvestDesc array in the same copy; the a-priori decode (a mode of ldpc_decode_kernel) runs IN FRONT of the three harvest launches and leaves a decode-record array
 // per channel in the group's AP staging, which is what HarvestDesc.msg then points at (.osd null); one annotate launch follows them.
 enum { FETCH_DECODES = 0, FETCH_REPORTS = 1, FETCH_AP = 2 };
@@ -1004,7 +1021,9 @@ static int fetch_decodes_impl(cwslg_ctx *c, int group, uint64_t *start_epoch, cw
     std::vector<ApDesc> adescs;
     ApBlock ap_block{};
     LdpcTables ap_tables{};
-    int ap_npat = 0, ap_max_iter = 0, ap_min_nsync = 0, ap_cap_max = 0;
+    int ap_npat = 0, ap_max_iter = 0, ap_min_nsync = 0, ap_min_nqual = 0, ap_cap_max = 0;
+    // AP staging per entry slot: FT8 a 20-byte record and its dmin; FT4 three slots per candidate, each a 60-byte record and three dmin
+    const size_t ap_per_cand = ft4 ? 3 * (sizeof(Ft4MsgRec) + 3 * sizeof(float)) : sizeof(Ft8MsgRec) + sizeof(float);
     Ft4Tables tb4{};
     const float2 *d_w32 = nullptr;
     const uint32_t *d_enc = nullptr;
@@ -1018,10 +1037,11 @@ static int fetch_decodes_impl(cwslg_ctx *c, int group, uint64_t *start_epoch, cw
         if (ap) {
             const SyncShared &s = c->sync_shared;
             if (!s.ldpc_loaded) return fail(c, CWSLG_ERR_ARG, "a-priori decoding needs a parity-check table (cwslg_set_ldpc_code)");
-            if (s.ap_npat <= 0) return fail(c, CWSLG_ERR_ARG, "no AP pattern set (cwslg_set_ft8_ap)");
-            std::memcpy(&ap_block, s.ap_block, sizeof(ApBlock));
+            if ((ft4 ? s.ap4_npat : s.ap_npat) <= 0) return fail(c, CWSLG_ERR_ARG, "no AP pattern set (%s)", ft4 ? "cwslg_set_ft4_ap" : "cwslg_set_ft8_ap");
+            std::memcpy(&ap_block, ft4 ? s.ap4_block : s.ap_block, sizeof(ApBlock));
             std::memcpy(&ap_tables, s.ldpc_tables, sizeof(LdpcTables));
-            ap_npat = s.ap_npat; ap_max_iter = s.ap_max_iter; ap_min_nsync = s.ap_min_nsync;
+            ap_npat = ft4 ? s.ap4_npat : s.ap_npat; ap_max_iter = ft4 ? s.ap4_max_iter : s.ap_max_iter;
+            ap_min_nsync = ft4 ? s.ap4_min_nsync : s.ap_min_nsync; ap_min_nqual = ft4 ? s.ap4_min_nqual : 0;
         }
         uint64_t E = *start_epoch;
         std::vector<std::pair<int, uint64_t>> live;
@@ -1050,9 +1070,10 @@ static int fetch_decodes_impl(cwslg_ctx *c, int group, uint64_t *start_epoch, cw
             if (ap) {           // (the staging pointers are filled in below, once its size is known)
                 ApDesc a{};
                 a.cnt = b.d_ncand;
-                a.soft = b.d_soft;
+                a.soft = ft4 ? (const void *)b.d_ft4soft : (const void *)b.d_soft;
                 a.msg = d.msg;
                 a.osd = d.osd;
+                a.nrec = d.nrec;
                 a.cap = d.cap;
                 adescs.push_back(a);
                 ap_cap_max = std::max(ap_cap_max, d.cap);
@@ -1088,10 +1109,11 @@ static int fetch_decodes_impl(cwslg_ctx *c, int group, uint64_t *start_epoch, cw
             d_w32 = s.ft4_w32;
         }
         if (ap) {
-            // the group's AP staging: per channel cap records of 20 bytes, then cap dmin words, each channel from a multiple of 16.  Only calls
-            // that hs.mu serialises and that synchronise before they return touch it: none is in flight now
+            // the group's AP staging: per channel cap records of 20 bytes (FT4: 3 cap of 60), then their dmin words (FT4: three per record),
+            // each channel from a multiple of 16.  Only calls that hs.mu serialises and that synchronise before they return touch it: none is
+            // in flight now
             size_t need = 0;
-            for (const ApDesc &a : adescs) need += ((size_t)a.cap * (sizeof(Ft8MsgRec) + sizeof(float)) + 15) & ~size_t(15);
+            for (const ApDesc &a : adescs) need += ((size_t)a.cap * ap_per_cand + 15) & ~size_t(15);
             if (hs.ap_bytes < need) {
                 if (hs.d_ap) (void)hipFree(hs.d_ap);
                 hs.d_ap = nullptr; hs.ap_bytes = 0;
@@ -1102,8 +1124,8 @@ static int fetch_decodes_impl(cwslg_ctx *c, int group, uint64_t *start_epoch, cw
             for (size_t i = 0; i < adescs.size(); ++i) {
                 ApDesc &a = adescs[i];
                 a.ap = hs.d_ap + at;
-                a.dmin = (float *)(hs.d_ap + at + (size_t)a.cap * sizeof(Ft8MsgRec));
-                at += ((size_t)a.cap * (sizeof(Ft8MsgRec) + sizeof(float)) + 15) & ~size_t(15);
+                a.dmin = (float *)(hs.d_ap + at + (size_t)a.cap * (ft4 ? 3 * sizeof(Ft4MsgRec) : sizeof(Ft8MsgRec)));
+                at += ((size_t)a.cap * ap_per_cand + 15) & ~size_t(15);
                 descs[i].msg = a.ap;
                 descs[i].osd = nullptr;
             }
@@ -1149,9 +1171,9 @@ static int fetch_decodes_impl(cwslg_ctx *c, int group, uint64_t *start_epoch, cw
     unsigned *d_out = (unsigned *)(hs.d + up_pad + 2 * cnt_bytes);
     HIPCHK(c, hipStreamWaitEvent(rf.fs, rf.ev, 0));
     HIPCHK(c, hipMemcpyAsync(hs.d, hs.h, up_bytes, hipMemcpyHostToDevice, rf.fs));
-    if (ap) ap_launch_chain(rf.fs, (const ApDesc *)(hs.d + adesc_at), (int)nch, ap_cap_max, ap_max_iter, ap_min_nsync, hs.d + atab_at, hs.d + apat_at, ap_npat);
+    if (ap) ap_launch_chain(rf.fs, (const ApDesc *)(hs.d + adesc_at), (int)nch, ap_cap_max, ap_max_iter, ap_min_nsync, hs.d + atab_at, hs.d + apat_at, ap_npat, ft4, ap_min_nqual);
     harvest_launch(rf.fs, d_desc, d_counts, d_offsets, d_out, (int)nch, (int)lim, ft4 ? 1 : 0);
-    if (ap) ap_launch_annotate(rf.fs, (const ApDesc *)(hs.d + adesc_at), d_offsets, d_out, (int)nch, (int)lim);
+    if (ap) ap_launch_annotate(rf.fs, (const ApDesc *)(hs.d + adesc_at), d_offsets, d_out, (int)nch, (int)lim, ft4);
     if (reports && ft4)
         ft4_report_launch(rf.fs, (const Ft4ReportDesc *)(hs.d + pad(desc_bytes)), d_offsets, d_out, d_enc, d_out + rep_at, tb4, d_w32, (int)nch, (int)lim);
     else if (reports)
@@ -1210,6 +1232,17 @@ int cwslg_fetch_ft8_ap(cwslg_ctx *c, uint64_t *start_epoch, cwslg_decode *dst, i
     if (n_channels) *n_channels = 0;
     if (!c || !start_epoch || !n || !n_total || (max > 0 && !dst)) return CWSLG_ERR_ARG;
     return fetch_decodes_impl(c, CWSLG_GROUP_FT8, start_epoch, dst, nullptr, max, n, n_total, n_channels, FETCH_AP);
+}
+
+// The a-priori words of the FT4 group (the header's "FT4 a-priori decoding"): the same path under the FT4 patterns -- a wave per (record slot,
+// metric set), the harvest's FT4 modes on the staging's three-set records.
+int cwslg_fetch_ft4_ap(cwslg_ctx *c, uint64_t *start_epoch, cwslg_decode *dst, int max, int *n, int *n_total, int *n_channels)
+{
+    if (n) *n = 0;
+    if (n_total) *n_total = 0;
+    if (n_channels) *n_channels = 0;
+    if (!c || !start_epoch || !n || !n_total || (max > 0 && !dst)) return CWSLG_ERR_ARG;
+    return fetch_decodes_impl(c, CWSLG_GROUP_FT4, start_epoch, dst, nullptr, max, n, n_total, n_channels, FETCH_AP);
 }
 
 // The channel tones of a 91-bit word under the code in force: the re-encoder of the reports on its own, host work only.

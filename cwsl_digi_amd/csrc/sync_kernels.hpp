@@ -85,6 +85,8 @@ struct SyncShared {
     bool enc_dirty = false;               // enc_gen is newer than the device copy
     uint32_t ap_block[8 * 6] = {};        // cwslg_set_ft8_ap: the patterns as the kernel reads them (ap_host.hpp: ApBlock); host bytes only -- every AP call uploads the block in force
     int ap_npat = 0, ap_max_iter = 30, ap_min_nsync = 7;
+    uint32_t ap4_block[8 * 6] = {};       // cwslg_set_ft4_ap: the FT4 patterns, a state of their own (on the air FT4's message bits are scrambled: a caller's FT4 patterns differ)
+    int ap4_npat = 0, ap4_max_iter = 30, ap4_min_nsync = 8, ap4_min_nqual = 20;
 };
 
 struct SyncChannelBuffers {

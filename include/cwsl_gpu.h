@@ -603,7 +603,7 @@ int cwslg_fetch_ft4_decode(cwslg_ctx *ctx, int ch_id, cwslg_ft4_msg *dst, int ma
  *       (first success wins) a false word in set 0 would be preferred to the true BP word in set 1.
  *   Which word "wins" is not stored: the smallest s with BP crc_ok; if there is none, the smallest s with OSD crc_ok, marked as found by OSD
  *       (cwslgpu::ft4BestWord in cwsl_gpu_shim.hpp, ft4_best_word in the Python package; -1 if none).  ft4BestSet / ft4_best_set are unchanged.
- *   Out of scope: rvec descrambling, a-priori passes, unpacking to text, de-duplication, extending cwslg_fetch_slot.
+ *   Out of scope: rvec descrambling, a-priori passes (a fetch of their own: FT4 a-priori decoding below), unpacking to text, de-duplication, extending cwslg_fetch_slot.
  * cwslg_enable_ft4_osd(ctx, 1, order 0..2, min_nsync 0..17, min_nqual 0..33) returns CWSLG_ERR_ARG unless a code of rank 83 is loaded and the
  * arguments are in range (17 and 33 mean "nothing is attempted", as for cwslg_enable_ft4_decode); switching it off is always allowed.  It takes
  * effect only at a boundary where the coherent stage, FT4 soft bits and the FT4 decode are all on: then one launch follows the decode launch on
@@ -644,8 +644,8 @@ int cwslg_fetch_ft4_osd(cwslg_ctx *ctx, int ch_id, cwslg_ft4_osd *dst, int max, 
 typedef struct {
     int32_t  ch_id;
     int16_t  entry;      /* FT8: index into the candidate list; FT4: index of the sync record as cwslg_fetch_ft4_sync compacts them */
-    uint8_t  by_osd;     /* 0: word of the decode record (BP); 1: word of the OSD record; 2 (cwslg_fetch_ft8_ap only): word of the AP record, set = its pattern */
-    uint8_t  set;        /* FT4: metric set 0..2 the word came from; FT8: 0 */
+    uint8_t  by_osd;     /* 0: word of the decode record (BP); 1: word of the OSD record; 2 (cwslg_fetch_ft8_ap, cwslg_fetch_ft4_ap only): word of the AP record */
+    uint8_t  set;        /* FT4: metric set 0..2 the word came from; FT8: 0.  by_osd 2: FT8 the pattern index p; FT4 s | p << 2 (set & 3 the metric set, set >> 2 the pattern) */
     uint8_t  bits[12];   /* as cwslg_ft8_msg.bits */
     float    freq_hz;    /* FT8: candidate freq_hz; FT4: record f1_hz */
     float    dt_s;       /* FT8: candidate dt_s; FT4: record dt_s */
@@ -782,13 +782,46 @@ int cwslg_ft4_tones(cwslg_ctx *ctx, const uint8_t *bits /* [12] */, uint8_t *ton
  * per candidate, the count read on the device), the three harvest launches run on its records, ONE further launch (another mode of that kernel)
  * annotates the emitted records, ONE copy down, one synchronise.  Staging: per taking-part channel max_cand x (20 + 4) bytes; it belongs to the
  * group, is allocated at the first call, grows, and is freed by cwslg_destroy: a context that never calls holds no byte of it.
- * Out of scope: FT4 AP, AP words inside cwslg_fetch_decodes itself, packing call signs into patterns, unpacking to text, signal subtraction, OSD
+ * Out of scope: AP words inside cwslg_fetch_decodes itself, packing call signs into patterns, unpacking to text, signal subtraction, OSD
  * on AP-modified metrics. */
 typedef struct { uint8_t mask[12]; uint8_t value[12]; } cwslg_ap_pattern;   /* codeword bits 0..90, packed as cwslg_ft8_msg.bits */
 typedef struct { cwslg_ft8_msg msg; float dmin; } cwslg_ap_msg;             /* 24 bytes; msg.pad_ = pattern index, 0xff: none */
 int cwslg_set_ft8_ap(cwslg_ctx *ctx, const cwslg_ap_pattern *pat, int n_pat, int max_iter, int min_nsync);
 int cwslg_fetch_ft8_ap(cwslg_ctx *ctx, uint64_t *start_epoch /* in/out */, cwslg_decode *dst, int max, int *n, int *n_total, int *n_channels);
 int cwslg_ap_decode(cwslg_ctx *ctx, const float *llr /* [n][174] */, int n, cwslg_ap_msg *out);
+/* FT4 a-priori decoding (PARITY UNPINNED like the rest of the chain): the FT4 sync records that belief propagation and OSD gave up on, decoded
+ * again under known-bit patterns -- the FT8 block above on the FT4 chain's three-set records.  Everything it needs is on the device after an FT4
+ * boundary; the alternative is 2112 bytes of metrics per failed record over the link and BP on the host.  A FETCH with a kernel inside, not a
+ * stage: no record kind, no stamp, no launch at a boundary, no field in cwslg_stats, stats.sync_launches untouched.  tests/ft4_ap_ref.py restates
+ * everything below in numpy, on tests/ap_ref.py.
+ *   Setter: cwslg_set_ft4_ap(ctx, pat, n_pat 0..8 (0 clears the patterns), max_iter 1..200, min_nsync 0..17, min_nqual 0..33) -- the ranges of
+ *       cwslg_enable_ft4_decode; 17 and 33 mean nothing is attempted.  The FT4 patterns are a state OF THEIR OWN beside the FT8 ones: on the air
+ *       FT4's 77 message bits are rvec-scrambled, so a caller's FT4 patterns hold the SCRAMBLED values and differ from their FT8 patterns.  No rvec
+ *       is applied anywhere in the library.  Validation is cwslg_set_ft8_ap's: CWSLG_ERR_ARG for an argument out of range, a bit at positions
+ *       91..95 or a value bit outside its mask; the patterns in force then stay.  Host effect only.
+ *   Gate, PER RECORD (for the reason the FT4 OSD gate gives: a consumer takes one word per record, and a record BP or OSD decoded in any set
+ *       has it).  A record is a sync record in the slot array: slot = 3 cand + r, r < nrec[cand].  It is TAKEN iff (1) no set of its
+ *       cwslg_ft4_msg has BP crc_ok; (2) if the channel's OSD records are used (point 3 of cwslg_fetch_decodes), no set of its cwslg_ft4_osd has
+ *       crc_ok; (3) its soft record has nsync >= min_nsync and nqual >= min_nqual.  Set s of a taken record is ATTEMPTED iff set[s].iters >= 0 in
+ *       the decode record (which covers sigma[s] == 0) and all 174 metrics llr[s][t] are finite.
+ *   Arithmetic: each attempted set follows rules 1 to 6 and the record rules of cwslg_ap_msg above on llr[s][0..173], unchanged.  The three sets of
+ *       a record run side by side, each to its own exit, as in the FT4 decode: no traffic between them, no early stop across them.  A set that is
+ *       not attempted gets the "not attempted" record.
+ *   Choice: a record's word is that of the SMALLEST s whose AP record has crc_ok.  The choice is SET-MAJOR: a find in set 0 under pattern 3 beats
+ *       a find in set 1 under pattern 0.  This is the library's own order; it has not been compared with upstream's.
+ * cwslg_fetch_ft4_ap is cwslg_fetch_decodes' contract for CWSLG_GROUP_FT4, points 1 to 7 above.  The harvest kernel's existing FT4 modes run
+ * unchanged on the AP records: entries in the order cwslg_fetch_ft4_sync compacts them, the all-zero word dropped, equal words of a channel
+ * folded by (nharderr, entry) with ndup, order ch_id then entry.  Every emitted record has by_osd = 2, set = s | p << 2 (s the metric set, p the
+ * pattern index: set & 3 and set >> 2) and dmin = that AP record's.  Words that BP or OSD already found on another entry are NOT removed: merge
+ * on the host as for FT8 (mergeApDecodes / merge_ap_decodes merge by (ch_id, bits) and serve unchanged).  CWSLG_ERR_ARG with no FT4 pattern set
+ * or no code loaded; CWSLG_ERR_NO_FRAME as for cwslg_fetch_decodes.  The call uses the patterns and tables IN FORCE AT THE CALL and takes them up
+ * in its own upload.  Execution: the FT8 call's, with one wave per (record slot, metric set) in the a-priori launch -- grid (ceil(9 max_cand / 4),
+ * taking-part channels), the FT4 decode's own exits -- and staging of 3 max_cand x (60 + 12) bytes per taking-part channel in the FT4 group's
+ * stage.  cwslg_ap_decode stays the flat twin under the FT8 patterns: the per-set arithmetic is the same kernel text.
+ * Out of scope: AP words inside cwslg_fetch_decodes itself, packing call signs into patterns, rvec, unpacking to text, OSD on AP-modified metrics,
+ * an early stop across the three sets of a record. */
+int cwslg_set_ft4_ap(cwslg_ctx *ctx, const cwslg_ap_pattern *pat, int n_pat, int max_iter, int min_nsync, int min_nqual);
+int cwslg_fetch_ft4_ap(cwslg_ctx *ctx, uint64_t *start_epoch /* in/out */, cwslg_decode *dst, int max, int *n, int *n_total, int *n_channels);
 int cwslg_fetch_slot(cwslg_ctx *ctx, int ch_id, int16_t *frame, size_t cap, void *list, size_t list_bytes,
                      cwslg_ft4_sync *ft4, int max_ft4, cwslg_slot_result *out);
 int cwslg_set_ft4_syncmin(cwslg_ctx *ctx, float syncmin);

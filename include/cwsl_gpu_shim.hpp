@@ -46,8 +46,8 @@ inline void check(cwslg_ctx *c, int rc)
     throw std::runtime_error("libcwslgpu: " + msg);
 }
 
-// What cwslg_fetch_ft8_ap leaves to the host: `decodes` (cwslg_fetch_decodes) followed by those records of `ap` (cwslg_fetch_ft8_ap, the same
-// epoch) whose bits[12] no record of `decodes` with the same ch_id carries -- BP / OSD win -- in ascending (ch_id, entry, by_osd).
+// What cwslg_fetch_ft8_ap and cwslg_fetch_ft4_ap leave to the host: `decodes` (cwslg_fetch_decodes) followed by those records of `ap` (the
+// a-priori call of the same group and epoch) whose bits[12] no record of `decodes` with the same ch_id carries -- BP / OSD win -- in ascending (ch_id, entry, by_osd).
 inline std::vector<cwslg_decode> mergeApDecodes(const std::vector<cwslg_decode> &decodes, const std::vector<cwslg_decode> &ap)
 {
     std::vector<cwslg_decode> out(decodes);
@@ -63,6 +63,12 @@ inline std::vector<cwslg_decode> mergeApDecodes(const std::vector<cwslg_decode> 
         return x.by_osd < y.by_osd;
     });
     return out;
+}
+
+// The `set` byte of an FT4 a-priori record (cwslg_fetch_ft4_ap: by_osd = 2) -> {metric set, pattern index}
+inline std::array<int, 2> apSetSplit(std::uint8_t set)
+{
+    return {set & 3, set >> 2};
 }
 
 // Which of a cwslg_ft4_msg's three sets a consumer takes: upstream tries the metric sets in order and stops at the first success, which is the
@@ -186,6 +192,26 @@ public:
         out.resize(max > 0 ? max : 0);
         int n = 0, total = 0;
         const int rc = cwslg_fetch_ft8_ap(c_, &startEpoch, out.data(), static_cast<int>(out.size()), &n, &total, nChannels);
+        if (rc == CWSLG_ERR_NO_FRAME) { out.clear(); return 0; }
+        check(c_, rc);
+        out.resize(n);
+        return total;
+    }
+    // FT4 a-priori decoding: patterns of their own beside the FT8 ones (FT4's message bits are scrambled on the air, so the values differ), the
+    // FT4 decode's two minima; fetchFt4Ap is fetchFt8Ap for the FT4 group, with set = metric set | pattern << 2 (apSetSplit).
+    void setFt4Ap(const cwslg_ap_pattern *patterns, int nPatterns, int maxIter = 30, int minNsync = 8, int minNqual = 20)
+    {
+        check(c_, cwslg_set_ft4_ap(c_, patterns, nPatterns, maxIter, minNsync, minNqual));
+    }
+    void setFt4Ap(const std::vector<cwslg_ap_pattern> &patterns, int maxIter = 30, int minNsync = 8, int minNqual = 20)
+    {
+        setFt4Ap(patterns.empty() ? nullptr : patterns.data(), static_cast<int>(patterns.size()), maxIter, minNsync, minNqual);
+    }
+    int fetchFt4Ap(std::vector<cwslg_decode> &out, std::uint64_t &startEpoch, int max = 4096, int *nChannels = nullptr)
+    {
+        out.resize(max > 0 ? max : 0);
+        int n = 0, total = 0;
+        const int rc = cwslg_fetch_ft4_ap(c_, &startEpoch, out.data(), static_cast<int>(out.size()), &n, &total, nChannels);
         if (rc == CWSLG_ERR_NO_FRAME) { out.clear(); return 0; }
         check(c_, rc);
         out.resize(n);
