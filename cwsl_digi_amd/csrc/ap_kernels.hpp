@@ -7,17 +7,15 @@
 // packs to.  This translation unit is built -ffp-contract=off: every product and sum below is one float32 operation.
 //
 // This is a FETCH with a kernel inside, not a stage (cwslg_fetch_ft8_ap, cwslg_fetch_ft4_ap): it reads the records the chain has left on the device and writes only
-// the group's staging.  The product library keeps one kernel per job and a test holds its count, so the a-priori work has no symbol of its own:
-// it is two further modes of ldpc_decode_kernel -- whose loop, LDS image and launch shape it shares -- behind one launch-uniform branch
-// (ApArgs::mode; ldpc_kernels.hpp), as the FT4 report is a mode of ft4_softbits_kernel:
-//   AP_DECODE    one wave per candidate, four per workgroup, grid (ceil(cap / 4), taking-part channels): the count is read on the device and the
+// the group's staging.  Two kernels, one per job; the decode shares ldpc_decode_kernel's loop (ldpc_bp_run), LDS image and launch shape:
+//   ap_decode_kernel    one wave per candidate, four per workgroup, grid (ceil(cap / 4), taking-part channels): the count is read on the device and the
 //                surplus waves leave.  The wave loads the graph ONCE (ldpc_graph_load: 23 values per lane, kept in registers across patterns).
 //                A pattern's six dwords of the 192-byte block are wave-uniform reads; per pattern the lane replaces the metrics of its bits l and
 //                l + 64 where the mask has them (bits 128..173 are never masked) and runs ldpc_bp_run, the ONE text of the loop, in the wave's LDS
 //                image.  A = 1.01f * max |llr| comes from a wave max reduction (exact in any order).  On success nharderr and dmin are taken
 //                against the ORIGINAL metrics: dmin is OSD's ordered chain (osd_dist over the error pattern, |llr| in the LDS image the loop has
-//                left), not a tree.  No cross-wave traffic, no workgroup barrier, every exit wave-uniform.  So that the hosting kernel keeps its
-//                registers (and the decode launch its occupancy), nothing but the graph stays live across a run: the original metrics of bits l and
+//                left), not a tree.  No cross-wave traffic, no workgroup barrier, every exit wave-uniform.  So that the kernel stays in the decode's
+//                register allocation (six waves per SIMD), nothing but the graph stays live across a run: the original metrics of bits l and
 //                l + 64 are read again per pattern, A and the pattern words are scalars.
 //                Three ways of finding llr and out, chosen by launch-uniform fields of ApArgs: desc != nullptr, candidate q of channel blockIdx.y
 //                behind the gate of the contract (its decode record attempted without crc_ok, its OSD record -- where used -- without crc_ok,
@@ -28,8 +26,8 @@
 //                the slot's decode record and, where used, of its OSD record, nsync and nqual of its Ft4SoftRec -- and per set iters >= 0;
 //                metrics llr[s] of the slot's soft record, record to set[s] of slot's Ft4MsgRec in the staging (= record q), dmin to dmin[q].
 //                All of that addressing is scalar (q goes through readfirstlane); everything behind it is the same text.
-//   AP_ANNOTATE  one thread per record decode_harvest_kernel has emitted from the AP records: the record's channel through `offsets` (as the
-//                report mode finds it), then by_osd = 2, set = the pattern index, dmin = the AP record's.  FT4: the metric set s from the set
+//   ap_annotate_kernel  one thread per record decode_harvest_kernel has emitted from the AP records: the record's channel through `offsets` (as
+//                decode_report_kernel finds it), then by_osd = 2, set = the pattern index, dmin = the AP record's.  FT4: the metric set s from the set
 //                byte the harvest wrote, the entry's slot by a serial walk over nrec (entry e is slot 3 k + (e - prefix(k)), prefix the running
 //                sum of min(max(nrec[k], 0), 3)), then set = s | pattern << 2 and dmin[3 slot + s].
 #pragma once
@@ -58,6 +56,18 @@ struct alignas(16) ApDesc {
     int pad_;
 };
 static_assert(sizeof(ApDesc) == 64, "descriptor layout");
+
+// What the two kernels are told; a field its kernel does not read stays 0 / null.
+struct ApArgs {
+    int n_pat;
+    const void *desc;                  // ApDesc[n_chan], or null: llr_flat / ap_flat
+    const void *pats;                  // ApBlock
+    void *ap_flat;                     // ApMsgRec[n_flat]
+    const unsigned *offsets;           // ap_annotate_kernel: the harvest's offsets and output block
+    unsigned *out;
+    int n_chan, max_out;
+    int ft4;                           // desc names FT4 channels: the slot layout, three sets per record
+};
 
 // a wave-uniform pointer, held in scalar registers
 template <typename T>
@@ -106,15 +116,15 @@ __device__ __forceinline__ void ap_annotate(const ApArgs &ap)
     rec[8] = as_global(reinterpret_cast<const unsigned *>(d->dmin))[entry];
 }
 
-// (declared in ldpc_kernels.hpp, in front of the kernel that calls it; s_v, s_z: the calling wave's LDS image)
-__device__ __forceinline__ void ap_modes(const ApArgs &ap, const float *llr_flat, int n_flat, int max_iter, int min_nsync, int min_nqual,
-                                         const LdpcTables *tables, float *s_v, float *s_z)
+__global__ __launch_bounds__(64 * LDPC_WAVES) void ap_annotate_kernel(ApArgs ap) { ap_annotate(ap); }
+
+__global__ __launch_bounds__(64 * LDPC_WAVES) void ap_decode_kernel(ApArgs ap, const float *__restrict__ llr_flat, int n_flat, int max_iter, int min_nsync,
+                                                                    int min_nqual, const LdpcTables *__restrict__ tables)
 {
-    if (ap.mode == AP_ANNOTATE) {
-        ap_annotate(ap);
-        return;
-    }
+    __shared__ __attribute__((aligned(16))) float s_vall[LDPC_WAVES][LDPC_VSIZE];
+    __shared__ __attribute__((aligned(16))) float s_zall[LDPC_WAVES][192];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    float *s_v = s_vall[wv], *s_z = s_zall[wv];               // the wave's LDS image
     const int q = (int)blockIdx.x * LDPC_WAVES + wv;
     const CWSLG_GLOBAL float *llr;
     CWSLG_GLOBAL uint32_t *ow, *od;                            // the 20-byte record, the dmin word
@@ -233,39 +243,34 @@ __device__ __forceinline__ void ap_modes(const ApArgs &ap, const float *llr_flat
     if (lane == 5) od[0] = __float_as_uint(dmin);
 }
 
-// The launches of the a-priori modes: ldpc_decode_kernel with the decode's own arguments null / 0.  The caller asks hipGetLastError.
-inline void ap_launch(hipStream_t s, dim3 grid, const float *llr, int n_flat, int max_iter, int min_nsync, const void *tables, const ApArgs &ap,
-                      int min_nqual = 0)
-{
-    hipLaunchKernelGGL(ldpc_decode_kernel, grid, dim3(64 * LDPC_WAVES), 0, s, (const SyncWork *)nullptr, (Ft8SoftRec *const *)nullptr, (Ft8MsgRec *const *)nullptr,
-                       llr, (Ft8MsgRec *)nullptr, n_flat, 0, max_iter, min_nsync, (const LdpcTables *)tables, (const Ft4Work *)nullptr,
-                       (Ft4SoftRec *const *)nullptr, (Ft4MsgRec *const *)nullptr, min_nqual, ap);
-}
-//   AP_DECODE on the n_chan channels of d_desc (cap_max: the largest cap among them); ft4: a wave per (record slot, metric set), 9 per candidate
+// The launches.  The caller asks hipGetLastError.
+//   ap_decode_kernel on the n_chan channels of d_desc (cap_max: the largest cap among them); ft4: a wave per (record slot, metric set), 9 per candidate
 inline void ap_launch_chain(hipStream_t s, const ApDesc *d_desc, int n_chan, int cap_max, int max_iter, int min_nsync, const void *tables,
                             const void *pats, int n_pat, bool ft4 = false, int min_nqual = 0)
 {
     if (n_chan <= 0 || cap_max <= 0) return;
     ApArgs ap{};
-    ap.mode = AP_DECODE; ap.n_pat = n_pat; ap.desc = d_desc; ap.pats = pats; ap.n_chan = n_chan; ap.ft4 = ft4 ? 1 : 0;
+    ap.n_pat = n_pat; ap.desc = d_desc; ap.pats = pats; ap.n_chan = n_chan; ap.ft4 = ft4 ? 1 : 0;
     const int waves = ft4 ? 9 * cap_max : cap_max;
-    ap_launch(s, dim3((unsigned)((waves + LDPC_WAVES - 1) / LDPC_WAVES), (unsigned)n_chan), nullptr, 0, max_iter, min_nsync, tables, ap, min_nqual);
+    hipLaunchKernelGGL(ap_decode_kernel, dim3((unsigned)((waves + LDPC_WAVES - 1) / LDPC_WAVES), (unsigned)n_chan), dim3(64 * LDPC_WAVES), 0, s, ap,
+                       (const float *)nullptr, 0, max_iter, min_nsync, min_nqual, (const LdpcTables *)tables);
 }
-//   AP_DECODE flat: n sets of 174 metrics, no gate
+//   ap_decode_kernel flat: n sets of 174 metrics, no gate
 inline void ap_launch_flat(hipStream_t s, const void *tables, const void *pats, int n_pat, const float *llr, ApMsgRec *out, int n, int max_iter)
 {
     if (n <= 0) return;
     ApArgs ap{};
-    ap.mode = AP_DECODE; ap.n_pat = n_pat; ap.pats = pats; ap.ap_flat = out;
-    ap_launch(s, dim3((unsigned)((n + LDPC_WAVES - 1) / LDPC_WAVES), 1), llr, n, max_iter, 0, tables, ap);
+    ap.n_pat = n_pat; ap.pats = pats; ap.ap_flat = out;
+    hipLaunchKernelGGL(ap_decode_kernel, dim3((unsigned)((n + LDPC_WAVES - 1) / LDPC_WAVES), 1), dim3(64 * LDPC_WAVES), 0, s, ap, llr, n, max_iter, 0, 0,
+                       (const LdpcTables *)tables);
 }
-//   AP_ANNOTATE behind harvest_launch on the same stream and blocks: a thread per record that emit may have written
+//   ap_annotate_kernel behind harvest_launch on the same stream and blocks: a thread per record that emit may have written
 inline void ap_launch_annotate(hipStream_t s, const ApDesc *d_desc, const unsigned *d_offsets, unsigned *d_out, int n_chan, int lim, bool ft4 = false)
 {
     if (lim <= 0) return;
     ApArgs ap{};
-    ap.mode = AP_ANNOTATE; ap.desc = d_desc; ap.offsets = d_offsets; ap.out = d_out; ap.n_chan = n_chan; ap.max_out = lim; ap.ft4 = ft4 ? 1 : 0;
-    ap_launch(s, dim3((unsigned)((lim + 64 * LDPC_WAVES - 1) / (64 * LDPC_WAVES))), nullptr, 0, 0, 0, nullptr, ap);
+    ap.desc = d_desc; ap.offsets = d_offsets; ap.out = d_out; ap.n_chan = n_chan; ap.max_out = lim; ap.ft4 = ft4 ? 1 : 0;
+    hipLaunchKernelGGL(ap_annotate_kernel, dim3((unsigned)((lim + 64 * LDPC_WAVES - 1) / (64 * LDPC_WAVES))), dim3(64 * LDPC_WAVES), 0, s, ap);
 }
 
 } // namespace cwslg

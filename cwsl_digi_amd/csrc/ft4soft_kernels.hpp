@@ -17,18 +17,17 @@
 // broadcasts) and the magnitudes stay in LDS.  Set 2's 25 groups go round the four waves, each lane holding four of a group's 256
 // magnitudes (index 4 lane + d): the two low index bits are reduced in the lane, the six lane bits by xor butterflies.
 //
-// cwslg_fetch_ft4_decode_reports adds a second, wave-uniform mode of the same symbol (FT4S_REPORT; the library keeps its kernel count): one
-// workgroup per emitted decode, launched ONCE behind decode_harvest_kernel's three launches on a fetch stream.  It finds the decode's channel
-// (binary search of the scan's offsets) and record slot (prefix over nrec[]), builds the SAME baseband and cs[103][4] through
-// ft4s_symbol_spectra -- one text for both modes -- and then one wave re-encodes the word (91 bits -> 174 -> 103 tones) and makes the 16-byte
-// cwslg_decode_report.  The soft-bit mode pays one scalar compare and branch for it.
+// cwslg_fetch_ft4_decode_reports adds a kernel of its own, ft4_report_kernel: one workgroup per emitted decode, launched ONCE
+// behind decode_harvest_kernel's three launches on a fetch stream.  It finds the decode's channel (binary search of the scan's offsets) and
+// record slot (prefix over nrec[]), builds the SAME baseband and cs[103][4] through ft4s_symbol_spectra -- one text for both kernels -- and
+// then one wave re-encodes the word (91 bits -> 174 -> 103 tones) and makes the 16-byte cwslg_decode_report.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "ft4sync_kernels.hpp"
 #include "ft8soft_kernels.hpp"
-#include "harvest_kernels.hpp"      // the record layout the report mode reads, report_pick6, REPORT_*
+#include "harvest_kernels.hpp"      // the record layout ft4_report_kernel reads, report_pick6, REPORT_*
 
 namespace cwslg {
 
@@ -43,9 +42,7 @@ constexpr int FT4S_ICOS4_V[16] = {0, 1, 3, 2, 1, 0, 2, 3, 2, 3, 1, 0, 3, 2, 0, 1
 constexpr int FT4S_QUAL_V[32] = {0, 0, 0, 1, 1, 0, 1, 1, 0, 1, 0, 0, 1, 1, 1, 0, 1, 1, 1, 0, 0, 1, 0, 0, 1, 0, 1, 1, 0, 0, 0, 1};
 constexpr unsigned FT4S_ICOS4 = ft4s_pack2(FT4S_ICOS4_V), FT4S_QUAL = ft4s_pack1(FT4S_QUAL_V);
 
-// ---- the decode reports' side of the kernel (cwslg_fetch_ft4_decode_reports; the contract is the header's, tests/ft4_decode_reports_ref.py
-// restates it) ----
-constexpr int FT4S_SOFT = 0, FT4S_REPORT = 1;
+// ---- the decode reports (cwslg_fetch_ft4_decode_reports; the contract is the header's, tests/ft4_decode_reports_ref.py restates it) ----
 // One channel that takes part in a report call, in an array of its own beside the HarvestDesc array (same index).
 struct alignas(16) Ft4ReportDesc {
     const float2 *cx;        // the channel's frame spectrum, [36289] (written by the boundary that made the records)
@@ -57,7 +54,7 @@ struct alignas(16) Ft4ReportDesc {
 };
 static_assert(sizeof(Ft4ReportDesc) == 48, "descriptor layout");
 struct Ft4ReportArgs {
-    int mode, n_chan, max_out, pad_;
+    int n_chan, max_out;
     const Ft4ReportDesc *rdesc;
     const unsigned *offsets;     // decode_harvest_kernel's scan: the first record of every channel
     const unsigned *out;         // its head and records
@@ -101,7 +98,7 @@ __device__ __forceinline__ void ft4s_symbol_spectra(const F4BaseLds &L, const fl
     __syncthreads();
 }
 
-// ---- FT4S_REPORT: the FT4 decode reports (cwslg_fetch_ft4_decode_reports) -----------------------------------------------------------------------
+// ---- ft4_report_kernel: the FT4 decode reports (cwslg_fetch_ft4_decode_reports) -----------------------------------------------------------------------
 // the tone of symbol n (0..102) of the codeword c0..c5 (OsdGen bit layout); *costas: n is a Costas symbol
 __device__ __forceinline__ int ft4r_tone(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned c4, unsigned c5, int n, bool *costas)
 {
@@ -195,7 +192,7 @@ __device__ __forceinline__ void ft4_report_finish(const Ft4ReportArgs &ra, const
     typedef unsigned v4u __attribute__((ext_vector_type(4)));
     const unsigned p = blockIdx.x;
 
-    // ---- the codeword: lane l owns encoder rows l and l + 64 (rows 64..90 on lanes 0..26); XOR across the lanes (as HARVEST_REPORT) ----
+    // ---- the codeword: lane l owns encoder rows l and l + 64 (rows 64..90 on lanes 0..26); XOR across the lanes (as decode_report_kernel) ----
     const int row_b = lane + 64 < REPORT_ENC_ROWS ? lane + 64 : lane;  // (a lane without a second row loads its first again and drops it)
     const CWSLG_GLOBAL v2u *ea = reinterpret_cast<const CWSLG_GLOBAL v2u *>(as_global(ra.enc) + (size_t)lane * REPORT_ENC_WORDS);
     const CWSLG_GLOBAL v2u *eb = reinterpret_cast<const CWSLG_GLOBAL v2u *>(as_global(ra.enc) + (size_t)row_b * REPORT_ENC_WORDS);
@@ -234,40 +231,41 @@ __device__ __forceinline__ void ft4_report_finish(const Ft4ReportArgs &ra, const
     }
 }
 
-// ra.mode (wave-uniform, a kernel argument) chooses between the two jobs of this ONE symbol: FT4S_SOFT, the boundary's soft bits (grid
-// (3 max_cand, FT4 channels); ra is otherwise unused), and FT4S_REPORT, the decode reports of a fetch (grid (records); works, soft and max_cand
-// are unused).  The soft-bit mode's stores are the ones it made before the report mode existed.
-__global__ __launch_bounds__(256) void ft4_softbits_kernel(const Ft4Work *__restrict__ works, Ft4SoftRec *const *__restrict__ soft,
-                                                           Ft4Tables tb, const float2 *__restrict__ w32, int max_cand, Ft4ReportArgs ra)
+// The decode reports of a fetch, grid (records).
+__global__ __launch_bounds__(256) void ft4_report_kernel(Ft4Tables tb, const float2 *__restrict__ w32, Ft4ReportArgs ra)
 {
     F4_BASE_LDS(L);
     __shared__ float2 s_cs[FT4S_NN][4];
     __shared__ __attribute__((aligned(16))) float s_mag[FT4S_NN][4];
-    __shared__ __attribute__((aligned(16))) float s_bm[3][256];            // the three metric sets, padded with +0; FT4S_REPORT: 16 words of scratch
+    __shared__ float2 s_w32[32];
+    __shared__ unsigned s_u[16];
+    const int tid = threadIdx.x;
+    Ft4ReportJob job;                                // what the spectra are made from: cx, f1_hz, ibest, and the word
+    if (!ft4_report_find(ra, s_u, &job)) return;
+    ft4s_symbol_spectra(L, job.cx, tb, w32, s_w32, s_cs, s_mag, job.f1, job.ibest, tid);
+    if ((tid >> 6) == 0) ft4_report_finish(ra, s_cs, s_mag, job.k0, job.k1, job.k2, tid & 63);
+}
+
+// The boundary's soft bits, grid (3 max_cand, FT4 channels).
+__global__ __launch_bounds__(256) void ft4_softbits_kernel(const Ft4Work *__restrict__ works, Ft4SoftRec *const *__restrict__ soft,
+                                                           Ft4Tables tb, const float2 *__restrict__ w32, int max_cand)
+{
+    F4_BASE_LDS(L);
+    __shared__ float2 s_cs[FT4S_NN][4];
+    __shared__ __attribute__((aligned(16))) float s_mag[FT4S_NN][4];
+    __shared__ __attribute__((aligned(16))) float s_bm[3][256];            // the three metric sets, padded with +0
     __shared__ float2 s_w32[32];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const bool report = ra.mode == FT4S_REPORT;
     const int slot = blockIdx.x;
-    Ft4ReportJob job;                                // what the spectra are made from: cx, f1_hz, ibest (+ the word, FT4S_REPORT)
-    if (report) {
-        if (!ft4_report_find(ra, reinterpret_cast<unsigned *>(&s_bm[0][0]), &job)) return;
-    } else {
-        const Ft4Work *w = works + blockIdx.y;
-        const int cand = slot / 3, r = slot - 3 * cand;
-        int ncand = *as_global(w->ncand);
-        if (ncand > max_cand) ncand = max_cand;
-        if (cand >= ncand) return;                      // workgroup-uniform, both
-        if (r >= as_global(w->nrec)[cand]) return;
-        const CWSLG_GLOBAL Ft4Rec *rec = as_global(w->rec) + slot;
-        job.cx = w->cx; job.f1 = rec->f1_hz; job.ibest = rec->ibest;
-        job.k0 = job.k1 = job.k2 = 0u;
-        for (int e = tid; e < 3 * 256; e += 256) (&s_bm[0][0])[e] = 0.0f;
-    }
-    ft4s_symbol_spectra(L, job.cx, tb, w32, s_w32, s_cs, s_mag, job.f1, job.ibest, tid);       // ONE text for both modes
-    if (report) {
-        if (wv == 0) ft4_report_finish(ra, s_cs, s_mag, job.k0, job.k1, job.k2, lane);
-        return;
-    }
+    const Ft4Work *w = works + blockIdx.y;
+    const int cand = slot / 3, r = slot - 3 * cand;
+    int ncand = *as_global(w->ncand);
+    if (ncand > max_cand) ncand = max_cand;
+    if (cand >= ncand) return;                      // workgroup-uniform, both
+    if (r >= as_global(w->nrec)[cand]) return;
+    const CWSLG_GLOBAL Ft4Rec *rec = as_global(w->rec) + slot;
+    for (int e = tid; e < 3 * 256; e += 256) (&s_bm[0][0])[e] = 0.0f;
+    ft4s_symbol_spectra(L, w->cx, tb, w32, s_w32, s_cs, s_mag, rec->f1_hz, rec->ibest, tid);
 
     // ---- nsync: lanes 0..15 of wave 0 take one Costas symbol each; first maximum over the tones (ties to the lowest tone)
     int nsync = 0;
@@ -368,7 +366,7 @@ __global__ __launch_bounds__(256) void ft4_softbits_kernel(const Ft4Work *__rest
 // The boundary's launch: one workgroup per record slot of every FT4 channel.
 inline void ft4_softbits_launch(hipStream_t s, const Ft4Work *d_works, Ft4SoftRec *const *d_soft, const Ft4Tables &tb, const float2 *d_w32, int max_cand, int n_chan)
 {
-    hipLaunchKernelGGL(ft4_softbits_kernel, dim3(3u * (unsigned)max_cand, (unsigned)n_chan), dim3(256), 0, s, d_works, d_soft, tb, d_w32, max_cand, Ft4ReportArgs{});
+    hipLaunchKernelGGL(ft4_softbits_kernel, dim3(3u * (unsigned)max_cand, (unsigned)n_chan), dim3(256), 0, s, d_works, d_soft, tb, d_w32, max_cand);
 }
 
 // The ONE further launch of cwslg_fetch_ft4_decode_reports, behind harvest_launch on the same stream and blocks: a workgroup per record that emit
@@ -379,9 +377,9 @@ inline void ft4_report_launch(hipStream_t s, const Ft4ReportDesc *d_rdesc, const
 {
     if (lim <= 0) return;
     Ft4ReportArgs ra{};
-    ra.mode = FT4S_REPORT; ra.n_chan = n_chan; ra.max_out = lim;
+    ra.n_chan = n_chan; ra.max_out = lim;
     ra.rdesc = d_rdesc; ra.offsets = d_offsets; ra.out = d_out; ra.enc = d_enc; ra.rep = d_rep;
-    hipLaunchKernelGGL(ft4_softbits_kernel, dim3((unsigned)lim), dim3(256), 0, s, (const Ft4Work *)nullptr, (Ft4SoftRec *const *)nullptr, tb, d_w32, 0, ra);
+    hipLaunchKernelGGL(ft4_report_kernel, dim3((unsigned)lim), dim3(256), 0, s, tb, d_w32, ra);
 }
 
 } // namespace cwslg

@@ -14,8 +14,8 @@
 // looks for equal keys -- counting them (ndup) and giving way to a better rank -- and a third ballot pass numbers the survivors.  Integer work
 // only; every global address goes through the global address space; no register array is indexed.
 //
-// cwslg_fetch_decode_reports adds a fourth mode of the same symbol, launched ONCE behind the three above (FT8 only):
-//   HARVEST_REPORT grid (ceil(min(n_total, max_out) / 4)): one WAVE per emitted record, no workgroup barrier -> the 16-byte cwslg_decode_report
+// cwslg_fetch_decode_reports adds a kernel of its own, launched ONCE behind the three above (FT8 only):
+//   decode_report_kernel  grid (ceil(min(n_total, max_out) / 4)): one WAVE per emitted record, no workgroup barrier -> the 16-byte cwslg_decode_report
 // of record p: the word is re-encoded (91 bits -> 174 -> 79 tones) with the systematic encoder of the loaded code and the channel's symbol-spectra
 // plane is read at the candidate's grid position, with ft8_softbits_kernel's addressing.  The arithmetic is the header's (cwslg_decode_report),
 // restated in tests/decode_reports_ref.py, bit for bit: this translation unit is built -ffp-contract=off.
@@ -27,7 +27,7 @@
 
 namespace cwslg {
 
-constexpr int HARVEST_COUNT = 0, HARVEST_SCAN = 1, HARVEST_EMIT = 2, HARVEST_REPORT = 3;
+constexpr int HARVEST_COUNT = 0, HARVEST_SCAN = 1, HARVEST_EMIT = 2;
 constexpr int HARVEST_NT = 256;
 constexpr int HARVEST_MAXSLOTS = 3 * SYNC_MAXCAND_CAP;                  // FT4: three record slots per candidate
 constexpr int HARVEST_REC_WORDS = 10;                                   // cwslg_decode is 40 bytes
@@ -47,7 +47,7 @@ struct alignas(16) HarvestDesc {
 };
 static_assert(sizeof(HarvestDesc) == 48, "descriptor layout");
 
-// What the report mode needs of the same channel, in an array of its own beside the HarvestDesc array (same index).
+// What decode_report_kernel needs of the same channel, in an array of its own beside the HarvestDesc array (same index).
 struct alignas(16) ReportDesc {
     const float *spectra;    // the channel's symbol-spectra plane, [372][nbins]
     const void *list;        // Cand[cap]
@@ -73,7 +73,7 @@ __device__ __forceinline__ unsigned harvest_place(bool flag, unsigned *s_w, unsi
     return before + (wave > 0 ? w0 : 0u) + (wave > 1 ? w1 : 0u) + (wave > 2 ? w2 : 0u);
 }
 
-// ---- HARVEST_REPORT ------------------------------------------------------------------------------------------------------------------------------
+// ---- decode_report_kernel ------------------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ unsigned report_pick6(unsigned w0, unsigned w1, unsigned w2, unsigned w3, unsigned w4, unsigned w5, int i)
 {
     return i == 0 ? w0 : i == 1 ? w1 : i == 2 ? w2 : i == 3 ? w3 : i == 4 ? w4 : w5;
@@ -114,7 +114,7 @@ __device__ __forceinline__ bool report_symbol(const float *pw, int n, int tone, 
     return km == tone;
 }
 
-// One wave per emitted record.  s_pw: the wave's [80][8] image of powers (2560 bytes of the workgroup's LDS, private to the wave).
+// One wave per emitted record.  s_pw: the wave's [80][8] image of powers (2560 bytes of LDS, private to the wave).
 __device__ __forceinline__ void harvest_report_wave(const ReportDesc *rdesc, const unsigned *offsets, const unsigned *out, const uint32_t *enc,
                                                     unsigned *rep, int n_chan, int max_out, float *s_pw)
 {
@@ -202,21 +202,23 @@ __device__ __forceinline__ void harvest_report_wave(const ReportDesc *rdesc, con
     }
 }
 
+__global__ __launch_bounds__(64 * FT8S_WAVES) void decode_report_kernel(const ReportDesc *__restrict__ rdesc, const unsigned *__restrict__ offsets,
+                                                                        const unsigned *__restrict__ out, const uint32_t *__restrict__ enc,
+                                                                        unsigned *__restrict__ rep, int n_chan, int max_out)
+{
+    __shared__ __attribute__((aligned(16))) float s_pw[FT8S_WAVES][(FT8S_NSYM + 1) * 8];
+    harvest_report_wave(rdesc, offsets, out, enc, rep, n_chan, max_out, s_pw[threadIdx.x >> 6]);
+}
+
 __global__ __launch_bounds__(HARVEST_NT) void decode_harvest_kernel(const HarvestDesc *__restrict__ desc, unsigned *__restrict__ counts,
                                                                     unsigned *__restrict__ offsets, unsigned *__restrict__ out, int n_chan, int max_out,
-                                                                    int ft4, int mode, const ReportDesc *__restrict__ rdesc,
-                                                                    const uint32_t *__restrict__ enc, unsigned *__restrict__ rep)
+                                                                    int ft4, int mode)
 {
-    __shared__ __attribute__((aligned(16))) unsigned s_key[3][HARVEST_MAXSLOTS];      // the word: bits[12] as three little-endian words; HARVEST_REPORT: four waves' power images
+    __shared__ __attribute__((aligned(16))) unsigned s_key[3][HARVEST_MAXSLOTS];      // the word: bits[12] as three little-endian words
     __shared__ unsigned s_rank[HARVEST_MAXSLOTS];        // by_osd << 28 | nharderr << 16 | entry: smaller is better, never equal
     __shared__ unsigned s_info[HARVEST_MAXSLOTS];        // slot | set << 12; after the de-duplication: | ndup << 16 | survivor << 15
     __shared__ unsigned s_w[4];
     const unsigned tid = threadIdx.x;
-    if (mode == HARVEST_REPORT) {
-        static_assert(FT8S_WAVES * 64 == HARVEST_NT && FT8S_WAVES * (FT8S_NSYM + 1) * 8 <= 3 * HARVEST_MAXSLOTS, "four power images fit s_key");
-        harvest_report_wave(rdesc, offsets, out, enc, rep, n_chan, max_out, reinterpret_cast<float *>(&s_key[0][0]) + (tid >> 6) * ((FT8S_NSYM + 1) * 8));
-        return;
-    }
     CWSLG_GLOBAL unsigned *g_counts = as_global_rw(counts), *g_offsets = as_global_rw(offsets), *g_out = as_global_rw(out);
 
     if (mode == HARVEST_SCAN) {
@@ -364,7 +366,7 @@ inline void harvest_launch(hipStream_t s, const HarvestDesc *d_desc, unsigned *d
     for (int mode : {HARVEST_COUNT, HARVEST_SCAN, HARVEST_EMIT}) {
         if (mode == HARVEST_EMIT && lim == 0) break;
         hipLaunchKernelGGL(decode_harvest_kernel, dim3(mode == HARVEST_SCAN ? 1u : (unsigned)n_chan), dim3(HARVEST_NT), 0, s, d_desc, d_counts, d_offsets, d_out,
-                           n_chan, lim, ft4 ? 1 : 0, mode, (const ReportDesc *)nullptr, (const uint32_t *)nullptr, (unsigned *)nullptr);
+                           n_chan, lim, ft4 ? 1 : 0, mode);
     }
 }
 
@@ -375,8 +377,8 @@ inline void report_launch(hipStream_t s, const ReportDesc *d_rdesc, const unsign
                           int n_chan, int lim)
 {
     if (lim <= 0) return;
-    hipLaunchKernelGGL(decode_harvest_kernel, dim3((unsigned)((lim + FT8S_WAVES - 1) / FT8S_WAVES)), dim3(HARVEST_NT), 0, s, (const HarvestDesc *)nullptr,
-                       (unsigned *)nullptr, const_cast<unsigned *>(d_offsets), const_cast<unsigned *>(d_out), n_chan, lim, 0, HARVEST_REPORT, d_rdesc, d_enc, d_rep);
+    hipLaunchKernelGGL(decode_report_kernel, dim3((unsigned)((lim + FT8S_WAVES - 1) / FT8S_WAVES)), dim3(64 * FT8S_WAVES), 0, s, d_rdesc, d_offsets, d_out, d_enc,
+                       d_rep, n_chan, lim);
 }
 
 } // namespace cwslg

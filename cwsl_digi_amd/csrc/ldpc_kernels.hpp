@@ -120,7 +120,7 @@ __device__ __forceinline__ void ldpc_graph_load(LdpcGraph &g, const CWSLG_GLOBAL
 }
 
 // The loop of the decode contract (steps 1-8 of cwslg_ft8_msg) on the metrics l0, l1, l2 of the lane's bits, in the wave's LDS image: the ONE
-// text of it, called by ldpc_decode_kernel and by its a-priori mode (ap_kernels.hpp: ap_modes), which runs it once per pattern.  A run starts from messages
+// text of it, called by ldpc_decode_kernel and by ap_decode_kernel (ap_kernels.hpp), which runs it once per pattern.  A run starts from messages
 // +0 whatever an earlier run of the wave left; at exit it = iters, nbad, and z0, z1, z2 the lane's z (cw = z > 0).
 __device__ __forceinline__ void ldpc_bp_run(LdpcGraph &g, float l0, float l1, float l2, int max_iter, float *s_v, float *s_z, int lane, int &it_out,
                                             int &nbad_out, float &z0, float &z1, float &z2)
@@ -158,36 +158,15 @@ __device__ __forceinline__ void ldpc_bp_run(LdpcGraph &g, float l0, float l1, fl
     nbad_out = nbad;
 }
 
-// FT8 a-priori decoding (ap_kernels.hpp) runs as further modes of THIS symbol -- the product library keeps one kernel per job and its count is
-// held by a test -- behind one launch-uniform branch at the top: the three addressing modes above never see more of it than that branch.
-struct ApArgs {
-    int mode;                          // AP_OFF: the decode; AP_DECODE / AP_ANNOTATE: ap_kernels.hpp
-    int n_pat;
-    const void *desc;                  // ApDesc[n_chan], or null: llr_flat / ap_flat
-    const void *pats;                  // ApBlock
-    void *ap_flat;                     // ApMsgRec[n_flat]
-    const unsigned *offsets;           // AP_ANNOTATE: the harvest's offsets and output block
-    unsigned *out;
-    int n_chan, max_out;
-    int ft4;                           // desc names FT4 channels: the slot layout, three sets per record (ap_kernels.hpp)
-};
-constexpr int AP_OFF = 0, AP_DECODE = 1, AP_ANNOTATE = 2;
-__device__ __forceinline__ void ap_modes(const ApArgs &ap, const float *llr_flat, int n_flat, int max_iter, int min_nsync, int min_nqual,
-                                         const LdpcTables *tables, float *s_v, float *s_z);
-
 __global__ __launch_bounds__(64 * LDPC_WAVES) void ldpc_decode_kernel(const SyncWork *__restrict__ works, Ft8SoftRec *const *__restrict__ soft,
                                                                       Ft8MsgRec *const *__restrict__ msg, const float *__restrict__ llr_flat,
                                                                       Ft8MsgRec *__restrict__ out_flat, int n_flat, int maxcand, int max_iter, int min_nsync,
                                                                       const LdpcTables *__restrict__ tables, const Ft4Work *__restrict__ works4,
                                                                       Ft4SoftRec *const *__restrict__ soft4, Ft4MsgRec *const *__restrict__ msg4,
-                                                                      int min_nqual, ApArgs ap)
+                                                                      int min_nqual)
 {
     __shared__ __attribute__((aligned(16))) float s_vall[LDPC_WAVES][LDPC_VSIZE];
     __shared__ __attribute__((aligned(16))) float s_zall[LDPC_WAVES][192];
-    if (ap.mode != AP_OFF) {                                   // uniform over the launch
-        ap_modes(ap, llr_flat, n_flat, max_iter, min_nsync, min_nqual, tables, s_vall[threadIdx.x >> 6], s_zall[threadIdx.x >> 6]);
-        return;
-    }
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int q = (int)blockIdx.x * LDPC_WAVES + wv;
     const CWSLG_GLOBAL float *llr;
@@ -250,5 +229,3 @@ __global__ __launch_bounds__(64 * LDPC_WAVES) void ldpc_decode_kernel(const Sync
 }
 
 } // namespace cwslg
-
-#include "ap_kernels.hpp"              // ap_modes: every translation unit that has the kernel has its a-priori modes

@@ -195,7 +195,7 @@ int long_sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
         const LongWork *d = (const LongWork *)wb->d;
         const FftbTables tb{s.p45.wa, s.p45.wn, s.p45.wb, s.p45.wfull};
         const unsigned n = (unsigned)nw;
-        hipLaunchKernelGGL(long_pack_kernel, dim3(WSPR_M / 256, n), dim3(256), LONG_PACK_LDS_WSPR, c->stream, d, 0);
+        hipLaunchKernelGGL(wspr_pack_kernel, dim3(WSPR_M / 256, n), dim3(256), 0, c->stream, d);
         // 45 x 1024: the VALU form is the faster one (0.63 against 1.14 ms per 128 frames: a 45-row product wastes 30 % of two 32-row
         // matrix tiles); CWSLG_LONG_VARIANT bit 1 selects the matrix-core form (same bits)
 #if CWSLG_LAB
@@ -212,7 +212,7 @@ int long_sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
 #endif
         hipLaunchKernelGGL((fftb_stage1_kernel<45, 1024>), dim3(1024 / 64, 1, n), dim3(FFTB_S1_NT), 0, c->stream, d, tb, tb.wfull, 1, 1);
         hipLaunchKernelGGL((fftb_stage2_kernel<45, 1024>), dim3((45 + 3) / 4, 1, n), dim3(256), 0, c->stream, d, tb, 1);
-        hipLaunchKernelGGL(long_pack_kernel, dim3((WSPR_IQ_LEN + 255) / 256, n), dim3(256), 0, c->stream, d, LONG_PACK_WSPR_IQ);
+        hipLaunchKernelGGL(wspr_iq_kernel, dim3((WSPR_IQ_LEN + 255) / 256, n), dim3(256), 0, c->stream, d);
         hipLaunchKernelGGL(wspr_spectra_kernel, dim3(WSPR_NFFTS, n), dim3(256), 0, c->stream, d, (const float2 *)s.d_w512, (const float *)s.d_win512);
         hipLaunchKernelGGL(wspr_peaks_kernel, dim3(n), dim3(512), 0, c->stream, d);
         hipLaunchKernelGGL(wspr_coarse_kernel, dim3(WSPR_MAXCAND, n), dim3(256), 0, c->stream, d, (const unsigned char *)s.d_pr3);
@@ -223,7 +223,7 @@ int long_sync_launch(cwslg_ctx *c, const std::vector<int> &emitted)
         const unsigned n = (unsigned)nf;
         Fst4wParams P; int nband = 0;
         (void)long_fst4w_params(c->long_cfg, &P, &nband);
-        hipLaunchKernelGGL(long_pack_kernel, dim3(F4W_M / 256, n), dim3(256), LONG_PACK_LDS_FST4W, c->stream, d, 1);
+        hipLaunchKernelGGL(fst4w_pack_kernel, dim3(F4W_M / 256, n), dim3(256), 0, c->stream, d);
 #if CWSLG_LAB
         if (c->long_variant & 1) hipLaunchKernelGGL((fftb_stage1_kernel<125, 256>), dim3(256 / 64, 23, n), dim3(FFTB_S1_NT), 0, c->stream, d, tb, tb.wfull, 0, 0);
         else

@@ -406,8 +406,7 @@ __global__ __launch_bounds__(256) void wspr_combine_kernel(const LongWork *__res
     }
 }
 
-// idat/qdat = conj(inverse output) / 1000 (double division, as `fftout/1000.0`), zero tail.  grid (IQ_LEN / 256, channels); the third body of
-// long_pack_kernel below (selector 2)
+// idat/qdat = conj(inverse output) / 1000 (double division, as `fftout/1000.0`), zero tail.  grid (IQ_LEN / 256, channels)
 __device__ __forceinline__ void wspr_iq(const LongWork *__restrict__ works)
 {
     const LongWork *w = works + blockIdx.y;
@@ -626,18 +625,18 @@ __device__ __forceinline__ void fst4w_pack(const LongWork *__restrict__ works, f
     }
 }
 
-// The two pack passes and WSPR's idat/qdat pass as ONE kernel (the product library's inventory is capped): `fst4w` selects the body, wave-uniformly
-// -- 0 wspr_pack, 1 fst4w_pack, 2 wspr_iq; each body is the instruction stream it was as a kernel of its own and takes the LDS it took (dynamic:
-// LONG_PACK_LDS_WSPR / _FST4W bytes at the launch, none for wspr_iq).
-constexpr unsigned LONG_PACK_LDS_WSPR = (WSPR_R * 256 + 256) * sizeof(float), LONG_PACK_LDS_FST4W = F4W_R * 256 * sizeof(float);
-constexpr int LONG_PACK_WSPR = 0, LONG_PACK_FST4W = 1, LONG_PACK_WSPR_IQ = 2;
-__global__ __launch_bounds__(256) void long_pack_kernel(const LongWork *__restrict__ works, int fst4w)
+// The two pack passes and WSPR's idat/qdat pass: three jobs, three kernels; each pack takes the LDS its deal needs.
+__global__ __launch_bounds__(256) void wspr_pack_kernel(const LongWork *__restrict__ works)
 {
-    extern __shared__ float s_pack[];
-    if (fst4w == LONG_PACK_WSPR_IQ) wspr_iq(works);
-    else if (fst4w) fst4w_pack(works, s_pack);
-    else wspr_pack(works, s_pack);
+    __shared__ float s_x[WSPR_R * 256 + 256];
+    wspr_pack(works, s_x);
 }
+__global__ __launch_bounds__(256) void fst4w_pack_kernel(const LongWork *__restrict__ works)
+{
+    __shared__ float s_x[F4W_R * 256];
+    fst4w_pack(works, s_x);
+}
+__global__ __launch_bounds__(256) void wspr_iq_kernel(const LongWork *__restrict__ works) { wspr_iq(works); }
 
 // c_bigfft(k) for k = jlo .. jlo + nband - 1.  grid (125, channels), 256 threads: the workgroup owns the residue c = k mod 125 and
 // its threads walk d (k = c + 125 dd), so Y's two operands Z_p[i] = y[p][c][d] and Z_p[M - i] = y[p][125 - c][255 - d] are read

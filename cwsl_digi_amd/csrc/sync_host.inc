@@ -148,14 +148,14 @@ void ldpc_launch_ft8(hipStream_t st, const void *tables, const SyncWork *works, 
 {
     hipLaunchKernelGGL(ldpc_decode_kernel, dim3((unsigned)((max_cand + LDPC_WAVES - 1) / LDPC_WAVES), (unsigned)n_chan), dim3(64 * LDPC_WAVES), 0, st, works, soft, msg,
                        (const float *)nullptr, (Ft8MsgRec *)nullptr, 0, max_cand, max_iter, min_nsync, (const LdpcTables *)tables, (const Ft4Work *)nullptr,
-                       (Ft4SoftRec *const *)nullptr, (Ft4MsgRec *const *)nullptr, 0, ApArgs{});
+                       (Ft4SoftRec *const *)nullptr, (Ft4MsgRec *const *)nullptr, 0);
 }
 //   flat: n sets of 174 metrics, no gate
 void ldpc_launch_flat(hipStream_t st, const void *tables, const float *llr, Ft8MsgRec *out, int n, int max_iter)
 {
     hipLaunchKernelGGL(ldpc_decode_kernel, dim3((unsigned)((n + LDPC_WAVES - 1) / LDPC_WAVES), 1), dim3(64 * LDPC_WAVES), 0, st, (const SyncWork *)nullptr,
                        (Ft8SoftRec *const *)nullptr, (Ft8MsgRec *const *)nullptr, llr, out, n, 0, max_iter, 0, (const LdpcTables *)tables, (const Ft4Work *)nullptr,
-                       (Ft4SoftRec *const *)nullptr, (Ft4MsgRec *const *)nullptr, 0, ApArgs{});
+                       (Ft4SoftRec *const *)nullptr, (Ft4MsgRec *const *)nullptr, 0);
 }
 //   FT4 chain: one wave per (record slot, metric set) of n_chan channels, 9 max_cand waves per channel
 void ldpc_launch_ft4(hipStream_t st, const void *tables, const Ft4Work *works4, Ft4SoftRec *const *soft4, Ft4MsgRec *const *msg4, size_t n_chan, int max_cand,
@@ -163,7 +163,7 @@ void ldpc_launch_ft4(hipStream_t st, const void *tables, const Ft4Work *works4, 
 {
     hipLaunchKernelGGL(ldpc_decode_kernel, dim3((unsigned)((9 * max_cand + LDPC_WAVES - 1) / LDPC_WAVES), (unsigned)n_chan), dim3(64 * LDPC_WAVES), 0, st,
                        (const SyncWork *)nullptr, (Ft8SoftRec *const *)nullptr, (Ft8MsgRec *const *)nullptr, (const float *)nullptr, (Ft8MsgRec *)nullptr, 0, max_cand,
-                       max_iter, min_nsync, (const LdpcTables *)tables, works4, soft4, msg4, min_nqual, ApArgs{});
+                       max_iter, min_nsync, (const LdpcTables *)tables, works4, soft4, msg4, min_nqual);
 }
 
 // osd_decode_kernel's three addressing modes
@@ -876,7 +876,7 @@ int cwslg_set_ft4_ap(cwslg_ctx *c, const cwslg_ap_pattern *pat, int n_pat, int m
     return set_ap_impl(c, pat, n_pat, max_iter, min_nsync, min_nqual, true);
 }
 
-// The a-priori decode (ap_kernels.hpp: a mode of ldpc_decode_kernel) on n sets of 174 metrics from host memory, no gate; synchronous (temporary device buffers, the context's stream).  The
+// The a-priori decode (ap_kernels.hpp: ap_decode_kernel) on n sets of 174 metrics from host memory, no gate; synchronous (temporary device buffers, the context's stream).  The
 // patterns and the tables of the code go up in front of the metrics: in | pattern block | tables | metrics | records.
 int cwslg_ap_decode(cwslg_ctx *c, const float *llr, int n, cwslg_ap_msg *out)
 {
@@ -1000,7 +1000,7 @@ int cwslg_fetch_ft4_osd(cwslg_ctx *c, int ch_id, cwslg_ft4_osd *dst, int max, in
 // switch under which sync_launch runs ft4_dft567 / ft4_fft64_unpack on the channel's Ft4Work (cx = d_cx).  d_cx therefore holds THAT frame's
 // spectrum, and the sync records read here are that boundary's too: no path hands a stale spectrum to the report.
 // a-priori (cwslg_fetch_ft8_ap, cwslg_fetch_ft4_ap; ap_kernels.hpp): an ApDesc per channel, the pattern block and the tables of the code in force go up
-// behind the HarvestDesc array in the same copy; the a-priori decode (a mode of ldpc_decode_kernel) runs IN FRONT of the three harvest launches and leaves a decode-record array
+// behind the HarvestDesc array in the same copy; the a-priori decode (ap_decode_kernel) runs IN FRONT of the three harvest launches and leaves a decode-record array
 // per channel in the group's AP staging, which is what HarvestDesc.msg then points at (.osd null); one annotate launch follows them.
 enum { FETCH_DECODES = 0, FETCH_REPORTS = 1, FETCH_AP = 2 };
 static int fetch_decodes_impl(cwslg_ctx *c, int group, uint64_t *start_epoch, cwslg_decode *dst, cwslg_decode_report *rep, int max, int *n, int *n_total,
@@ -1200,7 +1200,7 @@ int cwslg_fetch_decodes(cwslg_ctx *c, int group, uint64_t *start_epoch, cwslg_de
     return fetch_decodes_impl(c, group, start_epoch, dst, nullptr, max, n, n_total, n_channels, FETCH_DECODES);
 }
 
-// The same call with a signal report per decode (harvest_kernels.hpp: HARVEST_REPORT; the contract is the header's, cwslg_decode_report).
+// The same call with a signal report per decode (harvest_kernels.hpp: decode_report_kernel; the contract is the header's, cwslg_decode_report).
 int cwslg_fetch_decode_reports(cwslg_ctx *c, int group, uint64_t *start_epoch, cwslg_decode *dec, cwslg_decode_report *rep, int max, int *n, int *n_total,
                                int *n_channels)
 {
@@ -1212,7 +1212,7 @@ int cwslg_fetch_decode_reports(cwslg_ctx *c, int group, uint64_t *start_epoch, c
     return fetch_decodes_impl(c, group, start_epoch, dec, rep, max, n, n_total, n_channels, FETCH_REPORTS);
 }
 
-// The FT4 group's call (ft4soft_kernels.hpp: FT4S_REPORT; the contract is the header's, "FT4 signal reports").
+// The FT4 group's call (ft4soft_kernels.hpp: ft4_report_kernel; the contract is the header's, "FT4 signal reports").
 int cwslg_fetch_ft4_decode_reports(cwslg_ctx *c, uint64_t *start_epoch, cwslg_decode *dec, cwslg_decode_report *rep, int max, int *n, int *n_total,
                                    int *n_channels)
 {

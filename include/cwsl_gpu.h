@@ -687,7 +687,7 @@ int cwslg_fetch_decodes(cwslg_ctx *ctx, int group, uint64_t *start_epoch /* in/o
  * and every other group: CWSLG_ERR_ARG -- the FT4 chain keeps no symbol-aligned plane; its reports are cwslg_fetch_ft4_decode_reports below); dec receives byte-identical records to what
  * cwslg_fetch_decodes returns for that epoch and max; rep[p] is the report of dec[p]; either output pointer may be null (nothing is written
  * through it; the counts are the same).  Execution, one ticket and one serialised call of the group: the descriptors go up, the three harvest
- * launches run, ONE further launch (a mode of decode_harvest_kernel, one wave per record) runs over the min(n_total, max) emitted records, ONE
+ * launches run, ONE further launch (decode_report_kernel, one wave per record) runs over the min(n_total, max) emitted records, ONE
  * copy brings head, decodes and reports down, one synchronise.  The staging blocks are the group's, shared with cwslg_fetch_decodes and grown
  * in the same way; the encoder's 2184-byte device copy is made by the first report call after a (re)load of the code: a context that never asks
  * for reports holds no device byte of it.  It writes no record, list, stamp or statistic.
@@ -736,7 +736,7 @@ int cwslg_ft8_tones(cwslg_ctx *ctx, const uint8_t *bits /* [12] */, uint8_t *ton
  * byte-identical records to what cwslg_fetch_decodes returns for that epoch and max; rep[p] is the report of dec[p] (nsync 0..16, nsymerr 0..87);
  * either output pointer may be null.  Execution, one ticket and one serialised call of the group: the descriptors go up (a second per-channel
  * descriptor with the spectrum, the sync records, nrec and the capacity rides in the same copy), the three harvest launches run, ONE further
- * launch (a wave-uniform mode of ft4_softbits_kernel, one 256-thread workgroup per record, the grid sized by max) runs over the
+ * launch (ft4_report_kernel, one 256-thread workgroup per record, the grid sized by max) runs over the
  * min(n_total, max) emitted records, ONE copy brings head, decodes and reports down, one synchronise.  Staging and the encoder's device copy are
  * as for the FT8 call; the code IN FORCE AT THE CALL is used.  A channel takes part only if its decode records are of the frame's epoch, which
  * implies that the last boundary ran the coherent stage on it: the spectrum read is that frame's.
@@ -778,8 +778,8 @@ int cwslg_ft4_tones(cwslg_ctx *ctx, const uint8_t *bits /* [12] */, uint8_t *ton
  * modes, run on the AP records.  Each emitted record has by_osd = 2, set = the pattern index and dmin = the AP record's.  Words that another
  * entry of the channel already decoded by BP or OSD are NOT removed here: merge on the host by bits[12] per ch_id, BP / OSD winning
  * (mergeApDecodes in cwsl_gpu_shim.hpp, merge_ap_decodes in api.py).  CWSLG_ERR_ARG with no pattern set or no code loaded.  Execution, one
- * ticket and one serialised call of the group: descriptors, pattern block and tables go up in one copy, the a-priori decode runs (a mode of ldpc_decode_kernel: one wave
- * per candidate, the count read on the device), the three harvest launches run on its records, ONE further launch (another mode of that kernel)
+ * ticket and one serialised call of the group: descriptors, pattern block and tables go up in one copy, the a-priori decode runs (ap_decode_kernel: one wave
+ * per candidate, the count read on the device), the three harvest launches run on its records, ONE further launch (ap_annotate_kernel)
  * annotates the emitted records, ONE copy down, one synchronise.  Staging: per taking-part channel max_cand x (20 + 4) bytes; it belongs to the
  * group, is allocated at the first call, grows, and is freed by cwslg_destroy: a context that never calls holds no byte of it.
  * Out of scope: AP words inside cwslg_fetch_decodes itself, packing call signs into patterns, unpacking to text, signal subtraction, OSD

@@ -4,7 +4,7 @@ the answer is not empty; soft bits, decode and OSD order 1 on.  Per measured bou
   (a) the wall time of ONE cwslg_fetch_ft4_decode_reports call beside ONE cwslg_fetch_decodes(FT4) call on the same epoch (each also repeated
       once); the decodes of the two are compared byte for byte, and at the first measured boundary every report is compared with
       tests/ft4_decode_reports_ref.py on the frame spectrum and sync records of its channel;
-  (b) stats.sync_ms of the boundary itself, which the call is no part of but whose soft-bit kernel hosts the report mode: to be set against the
+  (b) stats.sync_ms of the boundary itself, which the call is no part of (when this was recorded the soft-bit kernel hosted the report as a mode): to be set against the
       parent commit's library (--sync-only runs of a checkout of it, in processes of their own, alternating with --sync-only runs of this tree).
 Median over the measured boundaries after a warm-up.
 

@@ -10,7 +10,7 @@ KEYS = ['s_waitcnt', 's_load_dwordx16', 's_load_dwordx8', 's_load_dwordx4', 's_l
 for name in sys.argv[2:]:
     for m in re.finditer(r'^(\S*%s\S*):[^\n]*\n' % re.escape(name), s, re.M):
         sym = m.group(1)
-        end = s.find('s_endpgm', m.end())
+        end = s.find('.Lfunc_end', m.end())              # (not the first s_endpgm: a kernel with an early exit has several)
         body = s[m.end():end]
         c = Counter(l.split()[0] for l in body.split('\n')
                     if l.strip() and not l.strip().startswith((';', '.')) and not l.strip().endswith(':'))

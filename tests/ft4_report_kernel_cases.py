@@ -1,4 +1,4 @@
-"""Test helper: the FT4S_REPORT mode of ft4_softbits_kernel (csrc/ft4soft_kernels.hpp) on frame spectra, sync records and decode records the test
+"""Test helper: ft4_report_kernel (csrc/ft4soft_kernels.hpp) on frame spectra, sync records and decode records the test
 writes -- the cases of tests/test_gpu_ft4_report_kernel.py, the file formats of tests/ft4_report_kernel_check.hip, and what the kernel must leave
 in its report block, computed by tests/ft4_decode_reports_ref.py alone (oracle.ft4_downsample -> ft4_softbits_ref.symbol_spectra -> the report).
 tests/test_ft4_report_kernel_inputs.py proves what the cases contain."""

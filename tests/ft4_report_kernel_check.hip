@@ -1,4 +1,4 @@
-// ft4_report_kernel_check.hip -- test tooling: the FT4S_REPORT mode of ft4_softbits_kernel (csrc/ft4soft_kernels.hpp) driven directly on frame
+// ft4_report_kernel_check.hip -- test tooling: ft4_report_kernel (csrc/ft4soft_kernels.hpp) driven directly on frame
 // spectra, sync records and decode records a test wrote, launched through ft4_report_launch as cwslg_fetch_ft4_decode_reports launches it, with
 // the tables the library uploads (ft4c_host_tables).  tests/ft4_report_kernel_cases.py writes the case file and reads the result file;
 // tests/test_gpu_ft4_report_kernel.py runs this program once for all cases.  Built with the product's flags, without -shared -fPIC.

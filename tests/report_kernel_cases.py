@@ -1,4 +1,4 @@
-"""Test helper: the HARVEST_REPORT mode of decode_harvest_kernel (csrc/harvest_kernels.hpp) on planes, lists and records the test writes -- the cases
+"""Test helper: decode_report_kernel (csrc/harvest_kernels.hpp) on planes, lists and records the test writes -- the cases
 of tests/test_gpu_report_kernel.py, the file formats of tests/report_kernel_check.hip, and what the kernel must leave in its report block,
 computed by tests/decode_reports_ref.py alone.  tests/test_report_kernel_inputs.py proves what the cases contain.
 

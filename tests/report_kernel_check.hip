@@ -1,4 +1,4 @@
-// report_kernel_check.hip -- test tooling: the HARVEST_REPORT mode of decode_harvest_kernel (csrc/harvest_kernels.hpp) driven directly on planes,
+// report_kernel_check.hip -- test tooling: decode_report_kernel (csrc/harvest_kernels.hpp) driven directly on planes,
 // lists and decode records a test wrote, launched through report_launch as cwslg_fetch_decode_reports launches it.  tests/report_kernel_cases.py
 // writes the case file and reads the result file; tests/test_gpu_report_kernel.py runs this program once for all cases.  Built with the
 // product's flags, without -shared -fPIC.

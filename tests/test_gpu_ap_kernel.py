@@ -1,4 +1,4 @@
-"""GPU: the a-priori decode (a mode of ldpc_decode_kernel) through cwslg_ap_decode against the numpy restatement (tests/ap_ref.py), BYTE FOR BYTE -- no tolerance anywhere: the mixed
+"""GPU: the a-priori decode (ap_decode_kernel) through cwslg_ap_decode against the numpy restatement (tests/ap_ref.py), BYTE FOR BYTE -- no tolerance anywhere: the mixed
 batch of tests/ap_cases.py at every size that changes the grid, under 1, 2 and 8 patterns; every hand-made case of tests/test_ap_ref.py; nothing
 written beyond record n; a second code and other patterns between calls; the argument errors."""
 import numpy as np

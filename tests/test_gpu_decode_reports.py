@@ -1,5 +1,5 @@
 """GPU: cwslg_fetch_decode_reports -- cwslg_fetch_decodes with a signal report per decode, made on the device (include/cwsl_gpu.h, "FT8 signal
-reports"; the HARVEST_REPORT mode of csrc/harvest_kernels.hpp).  Every comparison is byte for byte: `dec` against cwslg_fetch_decodes, `rep`
+reports"; decode_report_kernel of csrc/harvest_kernels.hpp).  Every comparison is byte for byte: `dec` against cwslg_fetch_decodes, `rep`
 against tests/decode_reports_ref.py applied to the GPU's own plane (cwslg_sync_debug_fetch what 0), list and decodes; nsync against the soft
 record's.  The slots are tests/decode_report_cases.py's (tests/test_decode_reports_inputs.py proves what they contain)."""
 import ctypes as C

@@ -1,5 +1,5 @@
 """GPU: cwslg_fetch_ft4_decode_reports -- cwslg_fetch_decodes(FT4) with a signal report per decode, made on the device (include/cwsl_gpu.h, "FT4
-signal reports"; the FT4S_REPORT mode of csrc/ft4soft_kernels.hpp).  Every comparison is byte for byte: `dec` against cwslg_fetch_decodes, `rep`
+signal reports"; ft4_report_kernel of csrc/ft4soft_kernels.hpp).  Every comparison is byte for byte: `dec` against cwslg_fetch_decodes, `rep`
 against tests/ft4_decode_reports_ref.py applied to the GPU's own frame spectrum (cwslg_sync_debug_fetch "ft4_cx"), sync records and decodes; nsync
 against the soft record's.  The slots are tests/ft4_decode_report_cases.py's (tests/test_ft4_decode_reports_inputs.py proves what they contain)."""
 import ctypes as C

@@ -1,4 +1,4 @@
-"""GPU: the FT4S_REPORT mode of ft4_softbits_kernel (csrc/ft4soft_kernels.hpp) alone, on frame spectra, sync records and decode records a test
+"""GPU: ft4_report_kernel (csrc/ft4soft_kernels.hpp) alone, on frame spectra, sync records and decode records a test
 wrote -- 1, 2, 3 and 5 decodes, 600 candidates whose entry -> slot prefix crosses the passes of 256 and ends in the last slot, f1_hz at both ends
 of the band and ibest at both extremes, a carrier halfway between two tones, the zero spectrum (every first maximum a tie), one huge term among
 small ones on the lanes where the sum's pairing changes, the XOR reduction over both row halves of the encoder, 1, 2 and 257 channels with empty

@@ -1,6 +1,6 @@
 """GPU: the GROUP fetches -- cwslg_fetch_decodes, cwslg_fetch_decode_reports (FT8) and cwslg_fetch_ft4_decode_reports -- raced against the next
 boundary, against each other and against a reload of the code.  These calls run real device work on a fetch stream with the context mutex
-released (decode_harvest_kernel; its report mode on the channel's symbol-spectra plane and list; the report mode of ft4_softbits_kernel on the
+released (decode_harvest_kernel; decode_report_kernel on the channel's symbol-spectra plane and list; ft4_report_kernel on the
 channel's frame spectrum and sync records), protected by the group's ticket, HarvestStage::mu and report_mu alone, while the next boundary
 overwrites every buffer they read.  The slots, clocks and helpers are those of tests/test_gpu_record_fetch_races.py; the expected values are
 tests/record_race_cases.py:group_expected(), computed on the CPU alone before a thread starts (tests/test_record_race_inputs.py vets them: any

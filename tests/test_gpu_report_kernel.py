@@ -1,4 +1,4 @@
-"""GPU: the HARVEST_REPORT mode of decode_harvest_kernel (csrc/harvest_kernels.hpp) alone, on planes, lists and records a test wrote -- wave
+"""GPU: decode_report_kernel (csrc/harvest_kernels.hpp) alone, on planes, lists and records a test wrote -- wave
 positions in the workgroup and the last partial workgroup, the plane's edges, row pitches 32 and 992, a plane of equal values, one huge among 78
 tiny terms, the XOR reduction over both row halves of the encoder, 1, 2 and 257 channels with empty ones first, last and in a row, a limit below
 and above the total.  tests/report_kernel_check.hip drives the kernel through report_launch, the launch of cwslg_fetch_decode_reports, once for
