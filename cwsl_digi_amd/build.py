@@ -14,6 +14,11 @@ LIB = os.path.join(LIBDIR, "libcwslgpu.so")
 # -DCWSLG_LAB=1: the measured alternatives of every kernel and the environment switches that select them (scripts/, A/B tests).
 # The product library above carries one kernel per job and reads no such switch.
 LAB_LIB = os.path.join(LIBDIR, "libcwslgpu_lab.so")
+# The FT8 subtractor's kernels: a code object of their own beside the libraries, loaded by either library with hipModuleLoad at the
+# first call that subtracts.  Its sources live in csrc/modules/, which sources() does not compile into the libraries.
+MODDIR = os.path.join(CSRC, "modules")
+FT8SUB_MODULE = os.path.join(LIBDIR, "cwslgpu_ft8sub.hsaco")
+MODULES = ((FT8SUB_MODULE, os.path.join(MODDIR, "ft8sub.hip")),)
 BINDIR = os.path.join(HERE, "bin")
 # (CWSLG_SKIMMER_BIN / CWSLG_REALTIME_BIN: other builds of the two host programs for the tests that drive them -- the ThreadSanitizer builds of
 # scripts/gpu_r5_tsan.sh; test tooling only, the programs themselves read no such variable)
@@ -32,6 +37,8 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-std=c++17"
 # CWSLG_HIPCC_EXTRA: extra compiler flags for a measurement build (-D switches of the A/B scripts); part of the source hash, so the library is rebuilt
 import shlex
 HIPCC_FLAGS += shlex.split(os.environ.get("CWSLG_HIPCC_EXTRA", ""))
+# a module is a bare code object (--genco) under the product's floating-point flags: its arithmetic is restated bit for bit by the tests
+MODULE_FLAGS = ["--genco", "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-slp-vectorize", "-std=c++17"]
 
 
 def sources():
@@ -46,23 +53,24 @@ def _source_hash():
     import hashlib
     h = hashlib.sha256()
     deps = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if os.path.isfile(os.path.join(CSRC, f))]
-    deps += [os.path.join(CSRC, sub, f) for sub in ("host", "lab") for f in sorted(os.listdir(os.path.join(CSRC, sub)))]
+    deps += [os.path.join(CSRC, sub, f) for sub in ("host", "lab", "modules") for f in sorted(os.listdir(os.path.join(CSRC, sub)))]
     deps.append(os.path.join(HERE, "..", "include", "cwsl_gpu.h"))
     for d in deps:
         h.update(os.path.basename(d).encode())
         h.update(open(d, "rb").read())
     h.update(" ".join(HIPCC_FLAGS).encode())
+    h.update(" ".join(MODULE_FLAGS).encode())
     return h.hexdigest()
 
 
 def _stale():
-    if not os.path.isfile(LIB) or not os.path.isfile(LAB_LIB) or not os.path.isfile(SKIMMER) or not os.path.isfile(REALTIME) or not os.path.isfile(HASHFILE):
+    if not all(os.path.isfile(m) for m, _ in MODULES) or not os.path.isfile(LIB) or not os.path.isfile(LAB_LIB) or not os.path.isfile(SKIMMER) or not os.path.isfile(REALTIME) or not os.path.isfile(HASHFILE):
         return True
     return open(HASHFILE).read().strip() != _source_hash()
 
 
 def build(force=False, verbose=False):
-    """Compile csrc/*.hip -> lib/libcwslgpu.so.  Raises if hipcc is missing or compilation fails."""
+    """Compile csrc/*.hip -> lib/libcwslgpu.so (and the lab library), csrc/modules/*.hip -> lib/*.hsaco.  Raises if hipcc is missing or compilation fails."""
     if not force and not _stale():
         return LIB
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
@@ -84,6 +92,12 @@ def build(force=False, verbose=False):
             if verbose:
                 print(" ".join(cmd))
             procs.append((subprocess.Popen(cmd), tmp, lib, cmd))
+        for mod, src in MODULES:
+            tmp = mod + ".tmp.%d" % os.getpid()
+            cmd = [hipcc] + MODULE_FLAGS + ["-o", tmp, src]
+            if verbose:
+                print(" ".join(cmd))
+            procs.append((subprocess.Popen(cmd), tmp, mod, cmd))
         try:
             for pr, tmp, lib, cmd in procs:
                 if pr.wait() != 0:

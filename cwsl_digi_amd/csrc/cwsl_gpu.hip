@@ -54,6 +54,7 @@
 #include "longsync_kernels.hpp"
 #include "harvest_kernels.hpp"
 #include "ap_kernels.hpp"
+#include "ft8sub_layout.hpp"
 
 namespace cwslg {
 
@@ -232,6 +233,20 @@ struct HarvestStage {
     size_t ap_bytes = 0;
 };
 
+// The FT8 subtractor (cwslg_subtract_ft8, cwslg_ft8_subtract_flat; ft8sub_host.inc): the code object with its two kernels, loaded by the first
+// call that needs it, the per-decode fit records and the FT8 group's residual block.  A context that never subtracts loads and
+// holds nothing.  The module handles are guarded by the context mutex; the blocks by harvest[0].mu, which serialises the group's calls.
+struct Ft8SubStage {
+    hipModule_t module = nullptr;
+    hipFunction_t fit = nullptr, apply = nullptr;
+    char *d_recs = nullptr;            // [emitted decodes][F8SUB_REC_WORDS]
+    size_t recs_bytes = 0;
+    float *d_resid = nullptr;          // [channels that took part][180000]
+    size_t resid_bytes = 0;
+    uint64_t resid_epoch = 0;          // the slot epoch the block holds residuals of (0: none)
+    std::vector<int> resid_chans;      // ch_id of every residual in the block, in its order
+};
+
 struct TimedSpan {
     hipEvent_t a, b;
     int kind;                          // 0 demod, 1 finalize, 2 sync stage (whole), 3 / 4 its FT8 spectra / search + selection kernels
@@ -325,6 +340,7 @@ struct cwslg_ctx {
     LongConfig long_cfg;
     LongShared long_shared;
     HarvestStage harvest[2];           // cwslg_fetch_decodes: [0] the FT8 group's, [1] the FT4 group's
+    Ft8SubStage ft8sub;
     std::mutex report_mu;              // the report calls of BOTH groups, one at a time: they share the encoder's device copy (taken after harvest[].mu, before mu)
     // side stream: optionally (CWSLG_SYNC_VARIANT bit 3) carries the FT8 candidate kernel next to the following demod launch
     hipStream_t side = nullptr;
@@ -1138,6 +1154,7 @@ int rendezvous_failed(cwslg_ctx *c, int rc)
 } // namespace
 
 // sync stage glue (kept in its own file so this one stays readable)
+#include "ft8sub_host.inc"
 #include "sync_host.inc"
 // multi-GPU rendezvous: callback hook + the built-in RCCL form
 #include "multi_gpu.inc"
@@ -1272,6 +1289,9 @@ void cwslg_destroy(cwslg_ctx *c)
         if (hs.d) (void)hipFree(hs.d);
         if (hs.d_ap) (void)hipFree(hs.d_ap);
     }
+    if (c->ft8sub.d_recs) (void)hipFree(c->ft8sub.d_recs);
+    if (c->ft8sub.d_resid) (void)hipFree(c->ft8sub.d_resid);
+    if (c->ft8sub.module) (void)hipModuleUnload(c->ft8sub.module);
     if (c->clk_h) (void)hipHostFree(c->clk_h);
     for (hipStream_t fs : c->fetch_stream) if (fs) { (void)hipStreamSynchronize(fs); (void)hipStreamDestroy(fs); }
     for (hipEvent_t e : c->fetch_ev) if (e) (void)hipEventDestroy(e);

@@ -1002,11 +1002,19 @@ int cwslg_fetch_ft4_osd(cwslg_ctx *c, int ch_id, cwslg_ft4_osd *dst, int max, in
 // a-priori (cwslg_fetch_ft8_ap, cwslg_fetch_ft4_ap; ap_kernels.hpp): an ApDesc per channel, the pattern block and the tables of the code in force go up
 // behind the HarvestDesc array in the same copy; the a-priori decode (ap_decode_kernel) runs IN FRONT of the three harvest launches and leaves a decode-record array
 // per channel in the group's AP staging, which is what HarvestDesc.msg then points at (.osd null); one annotate launch follows them.
-enum { FETCH_DECODES = 0, FETCH_REPORTS = 1, FETCH_AP = 2 };
+// subtraction (cwslg_subtract_ft8; ft8sub_host.inc, modules/ft8sub.hip): a SubDesc per channel goes up like the ReportDesc, the head comes down behind
+// the harvest launches (the fit records are sized by what was emitted), the module's fit and apply launches follow, and the 28-byte reports come
+// down behind the records in the same copy; the residuals stay on the device, in the group's block.
+enum { FETCH_DECODES = 0, FETCH_REPORTS = 1, FETCH_AP = 2, FETCH_SUBTRACT = 3 };
 static int fetch_decodes_impl(cwslg_ctx *c, int group, uint64_t *start_epoch, cwslg_decode *dst, cwslg_decode_report *rep, int max, int *n, int *n_total,
-                              int *n_channels, int what)
+                              int *n_channels, int what, cwslg_subtract_report *sub = nullptr)
 {
-    const bool reports = what == FETCH_REPORTS, ap = what == FETCH_AP;
+    const bool subtract = what == FETCH_SUBTRACT;
+    const bool reports = what == FETCH_REPORTS || subtract, ap = what == FETCH_AP;      // (subtract: the reports' encoder, serialisation and block layout)
+    static_assert(sizeof(cwslg_subtract_report) == F8SUB_REP_WORDS * sizeof(unsigned), "record layout");
+    const size_t rep_words = subtract ? F8SUB_REP_WORDS : REPORT_WORDS;
+    std::vector<SubDesc> sdescs;
+    std::vector<int> sub_chans;
     static_assert(sizeof(cwslg_decode) == HARVEST_REC_WORDS * sizeof(unsigned), "record layout");
     static_assert(sizeof(cwslg_decode_report) == sizeof(ReportRec), "record layout");
     const bool ft4 = group == CWSLG_GROUP_FT4;
@@ -1031,6 +1039,13 @@ static int fetch_decodes_impl(cwslg_ctx *c, int group, uint64_t *start_epoch, cw
     ResultFetch rf;                     // ticket + lifetime, released when the copy is done or the call fails
     {
         std::lock_guard<std::mutex> g(c->mu);
+        if (subtract) {
+            const uint32_t *unused = nullptr;
+            hipSetDevice(c->device);
+            int rc = ft8sub_encoder(c, &unused);        // (the code first: a table without systematic form is CWSLG_ERR_ARG whatever else is there)
+            if (!rc) rc = ft8sub_module(c);
+            if (rc) return rc;
+        }
         if (reports && !c->sync_shared.enc_ready)
             return fail(c, CWSLG_ERR_ARG, "%s", c->sync_shared.ldpc_loaded ? "decode reports need a systematic code: columns 91..173 of the loaded parity-check table are singular"
                                                                     : "decode reports need a parity-check table (cwslg_set_ldpc_code)");
@@ -1085,6 +1100,15 @@ static int fetch_decodes_impl(cwslg_ctx *c, int group, uint64_t *start_epoch, cw
                 r.cnt = b.d_ncand;
                 r.cap = d.cap;
                 rdescs4.push_back(r);
+            } else if (subtract) {
+                // (the device frame is the reference's 20 s buffer; the decoder's frame, and the subtractor's, is its first 15 s)
+                if (ch.frame_len < (size_t)F8SUB_N || ((uintptr_t)ch.d_frame[ch.frame_idx] & 15u))
+                    return fail(c, CWSLG_ERR_ARG, "channel %d: the subtractor needs a 16-byte aligned frame of at least %d samples", l.first, F8SUB_N);
+                SubDesc r{};
+                r.frame = ch.d_frame[ch.frame_idx];
+                r.n_valid = (int)std::min(ch.frame_valid, (size_t)F8SUB_N);
+                sdescs.push_back(r);               // (.resid: below, once the block is there)
+                sub_chans.push_back(l.first);
             } else if (reports) {
                 ReportDesc r{};
                 r.spectra = b.d_spectra;
@@ -1107,6 +1131,21 @@ static int fetch_decodes_impl(cwslg_ctx *c, int group, uint64_t *start_epoch, cw
             d_enc = (const uint32_t *)s.d_encgen;
             tb4 = c->ft4_tables;            // (FT4: built by the boundary that made the records)
             d_w32 = s.ft4_w32;
+        }
+        if (subtract) {
+            // the group's residual block, a frame per channel that takes part.  Only calls that hs.mu serialises and that synchronise before they
+            // return write it, and the residual fetches take hs.mu: none is in flight now.  Its epoch is withdrawn until this call has succeeded
+            Ft8SubStage &st = c->ft8sub;
+            st.resid_epoch = 0;
+            st.resid_chans.clear();
+            const size_t need = sdescs.size() * (size_t)F8SUB_N * sizeof(float);
+            if (st.resid_bytes < need) {
+                if (st.d_resid) (void)hipFree(st.d_resid);
+                st.d_resid = nullptr; st.resid_bytes = 0;
+                HIPCHK(c, hipMalloc((void **)&st.d_resid, need));
+                st.resid_bytes = need;
+            }
+            for (size_t i = 0; i < sdescs.size(); ++i) sdescs[i].resid = st.d_resid + i * (size_t)F8SUB_N;
         }
         if (ap) {
             // the group's AP staging: per channel cap records of 20 bytes (FT4: 3 cap of 60), then their dmin words (FT4: three per record),
@@ -1138,13 +1177,13 @@ static int fetch_decodes_impl(cwslg_ctx *c, int group, uint64_t *start_epoch, cw
     const size_t nch = descs.size(), lim = std::min((size_t)std::max(max, 0), bound);
     auto pad = [](size_t v) { return (v + 255) & ~size_t(255); };
     const size_t desc_bytes = nch * sizeof(HarvestDesc), cnt_bytes = pad(nch * sizeof(unsigned));
-    const size_t rdesc_bytes = ft4 ? rdescs4.size() * sizeof(Ft4ReportDesc) : rdescs.size() * sizeof(ReportDesc);
+    const size_t rdesc_bytes = subtract ? sdescs.size() * sizeof(SubDesc) : ft4 ? rdescs4.size() * sizeof(Ft4ReportDesc) : rdescs.size() * sizeof(ReportDesc);
     // a-priori: | HarvestDesc | ApDesc | pattern block | tables |, each from a multiple of 256
     const size_t adesc_at = pad(desc_bytes), apat_at = adesc_at + pad(adescs.size() * sizeof(ApDesc)), atab_at = apat_at + pad(sizeof(ApBlock));
     const size_t up_bytes = ap ? atab_at + sizeof(LdpcTables) : reports ? pad(desc_bytes) + rdesc_bytes : desc_bytes, up_pad = pad(up_bytes);
     // down: head | lim records | (reports: from the next 16-byte boundary) lim reports
     const size_t rec_words = HARVEST_HEAD_WORDS + lim * HARVEST_REC_WORDS, rep_at = (rec_words + 3) & ~size_t(3);
-    const size_t out_bytes = (reports ? rep_at + lim * REPORT_WORDS : rec_words) * sizeof(unsigned);
+    const size_t out_bytes = (reports ? rep_at + lim * rep_words : rec_words) * sizeof(unsigned);
     const size_t h_need = up_pad + out_bytes, d_need = up_pad + 2 * cnt_bytes + out_bytes;
     if (hs.h_bytes < h_need) {
         if (hs.h) (void)hipHostFree(hs.h);
@@ -1159,7 +1198,7 @@ static int fetch_decodes_impl(cwslg_ctx *c, int group, uint64_t *start_epoch, cw
         hs.d_bytes = pad(d_need + d_need / 2);
     }
     std::memcpy(hs.h, descs.data(), desc_bytes);
-    if (reports) std::memcpy(hs.h + pad(desc_bytes), ft4 ? (const void *)rdescs4.data() : (const void *)rdescs.data(), rdesc_bytes);
+    if (reports) std::memcpy(hs.h + pad(desc_bytes), subtract ? (const void *)sdescs.data() : ft4 ? (const void *)rdescs4.data() : (const void *)rdescs.data(), rdesc_bytes);
     if (ap) {
         std::memcpy(hs.h + adesc_at, adescs.data(), adescs.size() * sizeof(ApDesc));
         std::memcpy(hs.h + apat_at, &ap_block, sizeof(ApBlock));
@@ -1174,7 +1213,22 @@ static int fetch_decodes_impl(cwslg_ctx *c, int group, uint64_t *start_epoch, cw
     if (ap) ap_launch_chain(rf.fs, (const ApDesc *)(hs.d + adesc_at), (int)nch, ap_cap_max, ap_max_iter, ap_min_nsync, hs.d + atab_at, hs.d + apat_at, ap_npat, ft4, ap_min_nqual);
     harvest_launch(rf.fs, d_desc, d_counts, d_offsets, d_out, (int)nch, (int)lim, ft4 ? 1 : 0);
     if (ap) ap_launch_annotate(rf.fs, (const ApDesc *)(hs.d + adesc_at), d_offsets, d_out, (int)nch, (int)lim, ft4);
-    if (reports && ft4)
+    if (subtract) {
+        // what was emitted decides the size of the fit records: the head comes down first
+        Ft8SubStage &st = c->ft8sub;
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(h_out, d_out, HARVEST_HEAD_WORDS * sizeof(unsigned), hipMemcpyDeviceToHost, rf.fs));
+        HIPCHK(c, hipStreamSynchronize(rf.fs));
+        const size_t n_emit = std::min((size_t)h_out[0], lim), need = n_emit * F8SUB_REC_WORDS * sizeof(unsigned);
+        if (st.recs_bytes < need) {
+            if (st.d_recs) (void)hipFree(st.d_recs);
+            st.d_recs = nullptr; st.recs_bytes = 0;
+            HIPCHK(c, hipMalloc((void **)&st.d_recs, need + need / 2));
+            st.recs_bytes = need + need / 2;
+        }
+        HIPCHK(c, ft8sub_launch(st.fit, st.apply, rf.fs, (const SubDesc *)(hs.d + pad(desc_bytes)), d_offsets, d_out, d_enc, (unsigned *)st.d_recs, d_out + rep_at,
+                                (int)nch, (int)n_emit, (int)lim));
+    } else if (reports && ft4)
         ft4_report_launch(rf.fs, (const Ft4ReportDesc *)(hs.d + pad(desc_bytes)), d_offsets, d_out, d_enc, d_out + rep_at, tb4, d_w32, (int)nch, (int)lim);
     else if (reports)
         report_launch(rf.fs, (const ReportDesc *)(hs.d + pad(desc_bytes)), d_offsets, d_out, d_enc, d_out + rep_at, (int)nch, (int)lim);
@@ -1184,6 +1238,11 @@ static int fetch_decodes_impl(cwslg_ctx *c, int group, uint64_t *start_epoch, cw
     const size_t total = h_out[0], got = std::min(total, lim);
     if (got && dst) std::memcpy(dst, h_out + HARVEST_HEAD_WORDS, got * sizeof(cwslg_decode));
     if (got && rep) std::memcpy(rep, h_out + rep_at, got * sizeof(cwslg_decode_report));
+    if (got && sub) std::memcpy(sub, h_out + rep_at, got * sizeof(cwslg_subtract_report));
+    if (subtract) {
+        c->ft8sub.resid_chans = sub_chans;
+        c->ft8sub.resid_epoch = *start_epoch;
+    }
     *n = (int)got;
     *n_total = (int)total;
     if (n_channels) *n_channels = (int)nch;
@@ -1262,6 +1321,120 @@ static int tones_impl(cwslg_ctx *c, const uint8_t *bits, uint8_t *tones, bool ft
 }
 int cwslg_ft8_tones(cwslg_ctx *c, const uint8_t *bits, uint8_t *tones) { return tones_impl(c, bits, tones, false); }
 int cwslg_ft4_tones(cwslg_ctx *c, const uint8_t *bits, uint8_t *tones) { return tones_impl(c, bits, tones, true); }
+
+// FT8 signal subtraction (the header's "FT8 signal subtraction"; ft8sub_host.inc): the report call's path with the module's two launches.
+int cwslg_subtract_ft8(cwslg_ctx *c, uint64_t *start_epoch, cwslg_decode *dec, cwslg_subtract_report *sub, int max, int *n, int *n_total, int *n_channels)
+{
+    if (n) *n = 0;
+    if (n_total) *n_total = 0;
+    if (n_channels) *n_channels = 0;
+    if (!c || !start_epoch || !n || !n_total) return CWSLG_ERR_ARG;
+    return fetch_decodes_impl(c, CWSLG_GROUP_FT8, start_epoch, dec, nullptr, max, n, n_total, n_channels, FETCH_SUBTRACT, sub);
+}
+
+// A channel's residual: valid only while the block's epoch is the channel's frame epoch.  *slot: its place in the block.  Caller holds
+// harvest[0].mu and c->mu.
+static int residual_slot(cwslg_ctx *c, int ch_id, size_t *slot, uint64_t *start_epoch)
+{
+    if (ch_id < 0 || ch_id >= (int)c->chans.size() || !c->chans[ch_id].open) return fail(c, CWSLG_ERR_ARG, "bad channel id");
+    const Channel &ch = c->chans[ch_id];
+    const Ft8SubStage &st = c->ft8sub;
+    if (!ch.have_frame || !st.resid_epoch || ch.frame_t0 != st.resid_epoch) return CWSLG_ERR_NO_FRAME;
+    const auto it = std::find(st.resid_chans.begin(), st.resid_chans.end(), ch_id);
+    if (it == st.resid_chans.end()) return CWSLG_ERR_NO_FRAME;
+    *slot = (size_t)(it - st.resid_chans.begin());
+    if (start_epoch) *start_epoch = st.resid_epoch;
+    return CWSLG_OK;
+}
+
+int cwslg_fetch_ft8_residual(cwslg_ctx *c, int ch_id, float *dst, size_t cap, size_t *n_valid, uint64_t *start_epoch)
+{
+    if (n_valid) *n_valid = 0;
+    if (!c || !dst) return CWSLG_ERR_ARG;
+    std::lock_guard<std::mutex> serial(c->harvest[0].mu);
+    std::lock_guard<std::mutex> g(c->mu);
+    size_t slot = 0;
+    const int rc = residual_slot(c, ch_id, &slot, start_epoch);
+    if (rc) return rc;
+    if (cap < (size_t)F8SUB_N) return fail(c, CWSLG_ERR_ARG, "destination holds %zu samples, a residual has %d", cap, F8SUB_N);
+    hipSetDevice(c->device);
+    // (the call that wrote the block synchronised its stream before it returned)
+    HIPCHK(c, hipMemcpyAsync(dst, c->ft8sub.d_resid + slot * (size_t)F8SUB_N, (size_t)F8SUB_N * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (n_valid) *n_valid = (size_t)F8SUB_N;
+    return CWSLG_OK;
+}
+
+int cwslg_ft8_residual_device_ptr(cwslg_ctx *c, int ch_id, const float **d_f32, uint64_t *start_epoch)
+{
+    if (d_f32) *d_f32 = nullptr;
+    if (!c || !d_f32) return CWSLG_ERR_ARG;
+    std::lock_guard<std::mutex> serial(c->harvest[0].mu);
+    std::lock_guard<std::mutex> g(c->mu);
+    size_t slot = 0;
+    const int rc = residual_slot(c, ch_id, &slot, start_epoch);
+    if (rc) return rc;
+    *d_f32 = c->ft8sub.d_resid + slot * (size_t)F8SUB_N;
+    return CWSLG_OK;
+}
+
+// The same two kernels on caller-supplied frames and items: temporary device buffers, the context's stream, synchronous (cwslg_ldpc_decode's
+// pattern).  The items are laid out as the harvest lays out its records (head, 10 dwords each, per-frame offsets), which is what the kernels read.
+int cwslg_ft8_subtract_flat(cwslg_ctx *c, const float *audio, int n_frames, const cwslg_ft8_sub_item *items, int n_items, cwslg_subtract_report *sub,
+                            float *residual)
+{
+    if (!c || n_frames < 1 || n_items < 0 || !audio || (n_items > 0 && (!items || !sub))) return CWSLG_ERR_ARG;
+    std::lock_guard<std::mutex> report_serial(c->report_mu);       // (the encoder's device copy, as the report calls)
+    std::lock_guard<std::mutex> g(c->mu);
+    std::vector<unsigned> offsets((size_t)n_frames, 0u), out((size_t)HARVEST_HEAD_WORDS + (size_t)n_items * HARVEST_REC_WORDS, 0u);
+    out[0] = (unsigned)n_items;
+    int frame = 0;
+    for (int i = 0; i < n_items; ++i) {
+        const cwslg_ft8_sub_item &it = items[i];
+        if (it.frame < frame || it.frame >= n_frames) return fail(c, CWSLG_ERR_ARG, "item %d: frame %d out of range or not in ascending order", i, it.frame);
+        if (!(it.freq_hz >= 0.0f && it.freq_hz <= 6000.0f) || !(it.dt_s >= -30.0f && it.dt_s <= 30.0f))
+            return fail(c, CWSLG_ERR_ARG, "item %d: freq_hz outside 0..6000 or dt_s outside -30..30", i);
+        while (frame < it.frame) offsets[++frame] = (unsigned)i;
+        unsigned *o = out.data() + HARVEST_HEAD_WORDS + (size_t)i * HARVEST_REC_WORDS;
+        o[0] = (unsigned)it.frame;
+        std::memcpy(o + 2, it.bits, 12);
+        std::memcpy(o + 5, &it.freq_hz, 4);
+        std::memcpy(o + 6, &it.dt_s, 4);
+    }
+    while (frame < n_frames - 1) offsets[++frame] = (unsigned)n_items;
+    hipSetDevice(c->device);
+    const uint32_t *d_enc = nullptr;
+    int rc = ft8sub_encoder(c, &d_enc);
+    if (!rc) rc = ft8sub_module(c);
+    if (rc) return rc;
+    auto pad = [](size_t v) { return (v + 255) & ~size_t(255); };
+    const size_t frame_bytes = (size_t)n_frames * F8SUB_N * sizeof(float);
+    const size_t desc_at = 2 * pad(frame_bytes), off_at = desc_at + pad((size_t)n_frames * sizeof(SubDesc)), out_at = off_at + pad(offsets.size() * sizeof(unsigned));
+    const size_t rep_at = out_at + pad(out.size() * sizeof(unsigned)), recs_at = rep_at + pad((size_t)n_items * F8SUB_REP_WORDS * sizeof(unsigned));
+    const size_t total = recs_at + (size_t)n_items * F8SUB_REC_WORDS * sizeof(unsigned);
+    char *d = nullptr;
+    HIPCHK(c, hipMalloc((void **)&d, total));
+    std::vector<SubDesc> descs((size_t)n_frames);
+    for (int f = 0; f < n_frames; ++f) {
+        descs[f].frame = (const float *)d + (size_t)f * F8SUB_N;
+        descs[f].resid = (float *)(d + pad(frame_bytes)) + (size_t)f * F8SUB_N;
+        descs[f].n_valid = F8SUB_N;
+    }
+    hipError_t e = hipMemcpyAsync(d, audio, frame_bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + desc_at, descs.data(), descs.size() * sizeof(SubDesc), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + off_at, offsets.data(), offsets.size() * sizeof(unsigned), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d + out_at, out.data(), out.size() * sizeof(unsigned), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess)
+        e = ft8sub_launch(c->ft8sub.fit, c->ft8sub.apply, c->stream, (const SubDesc *)(d + desc_at), (const unsigned *)(d + off_at), (const unsigned *)(d + out_at), d_enc,
+                          (unsigned *)(d + recs_at), (unsigned *)(d + rep_at), n_frames, n_items, n_items);
+    if (e == hipSuccess && n_items > 0) e = hipMemcpyAsync(sub, d + rep_at, (size_t)n_items * sizeof(cwslg_subtract_report), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && residual) e = hipMemcpyAsync(residual, d + pad(frame_bytes), frame_bytes, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t es = hipStreamSynchronize(c->stream);       // (the host vectors above live until here)
+    (void)hipFree(d);
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(c, CWSLG_ERR_HIP, "cwslg_ft8_subtract_flat failed: %s", hipGetErrorString(e));
+    return CWSLG_OK;
+}
 
 int cwslg_sync_debug_fetch(cwslg_ctx *c, int ch_id, int what, void *dst, size_t cap_bytes, size_t *n_items, int *row_len)
 {

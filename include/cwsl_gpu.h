@@ -423,7 +423,7 @@ int cwslg_fetch_ft8_softbits(cwslg_ctx *ctx, int ch_id, cwslg_ft8_soft *dst, int
 /* FT8 decode (row a13; PARITY UNPINNED): flooding sum-product decoding of the LDPC(174,91) code on the 174 metrics of every cwslg_ft8_soft record,
  * then the CRC-14 -- the first consumer of those metrics, on the device: per candidate 91 bits, "is a codeword", "CRC matches" and an iteration
  * count (20 bytes) instead of 704 bytes over the link and belief propagation on the host.  Structured like upstream bpdecode174_91.  Out of scope:
- * ordered-statistics decoding (a stage of its own: FT8 OSD below), a-priori passes (a fetch of their own: FT8 a-priori decoding below), signal subtraction, unpacking the 77 bits into text.  De-duplication (neighbouring candidates of
+ * ordered-statistics decoding (a stage of its own: FT8 OSD below), a-priori passes (a fetch of their own: FT8 a-priori decoding below), signal subtraction (a fetch of its own: FT8 signal subtraction below; a second pass over its residual stays out), unpacking the 77 bits into text.  De-duplication (neighbouring candidates of
  * one transmission repeat one message) is not this stage's either: cwslg_fetch_decodes below hands the words of a whole group out chosen and de-duplicated.  Off by default; while it is off nothing changes (launches, buffers, upload bytes, lists, records).
  *   The code is DATA THE CALLER LOADS: the WSJT-X source is not part of this repository and its parity-check table is not reproduced here.
  *       cwslg_set_ldpc_code takes the 83 x 7 table `Nm` of the integrator's own WSJT-X tree (recalled, not checked here, as lib/ft8/ldpc_174_91_c_parity.f90), row-major: entry =
@@ -693,7 +693,8 @@ int cwslg_fetch_decodes(cwslg_ctx *ctx, int group, uint64_t *start_epoch /* in/o
  * for reports holds no device byte of it.  It writes no record, list, stamp or statistic.
  * The report uses the code IN FORCE AT THE CALL: words decoded under an earlier table are re-encoded under the new one (their first 91 bits are
  * kept; parity, tones and therefore the figures are the new code's).
- * Out of scope: unpacking to text, signal subtraction, xsnr2 (FT4 reports: the next block). */
+ * Out of scope: unpacking to text, xsnr2, a second search pass over the residual frame (the subtraction itself is cwslg_subtract_ft8 below;
+ * FT4 reports: the next block). */
 typedef struct {
     float   snr_db;      /* see above; never below -24 (FT4: -21) */
     float   xsig;        /* power at the re-encoded tones */
@@ -740,7 +741,8 @@ int cwslg_ft8_tones(cwslg_ctx *ctx, const uint8_t *bits /* [12] */, uint8_t *ton
  * min(n_total, max) emitted records, ONE copy brings head, decodes and reports down, one synchronise.  Staging and the encoder's device copy are
  * as for the FT8 call; the code IN FORCE AT THE CALL is used.  A channel takes part only if its decode records are of the frame's epoch, which
  * implies that the last boundary ran the coherent stage on it: the spectrum read is that frame's.
- * Out of scope: unpacking to text, rvec, a-priori passes, signal subtraction, a baseline-referred SNR. */
+ * Out of scope: unpacking to text, rvec, a-priori passes, a baseline-referred SNR, FT4 signal subtraction and any second pass over a residual
+ * (FT8 has the subtraction, cwslg_subtract_ft8; the second pass stays out there too). */
 int cwslg_fetch_ft4_decode_reports(cwslg_ctx *ctx, uint64_t *start_epoch /* in/out */, cwslg_decode *dec, cwslg_decode_report *rep, int max,
                                    int *n, int *n_total, int *n_channels);
 int cwslg_ft4_tones(cwslg_ctx *ctx, const uint8_t *bits /* [12] */, uint8_t *tones /* [103] */);
@@ -782,7 +784,7 @@ int cwslg_ft4_tones(cwslg_ctx *ctx, const uint8_t *bits /* [12] */, uint8_t *ton
  * per candidate, the count read on the device), the three harvest launches run on its records, ONE further launch (ap_annotate_kernel)
  * annotates the emitted records, ONE copy down, one synchronise.  Staging: per taking-part channel max_cand x (20 + 4) bytes; it belongs to the
  * group, is allocated at the first call, grows, and is freed by cwslg_destroy: a context that never calls holds no byte of it.
- * Out of scope: AP words inside cwslg_fetch_decodes itself, packing call signs into patterns, unpacking to text, signal subtraction, OSD
+ * Out of scope: AP words inside cwslg_fetch_decodes itself, packing call signs into patterns, unpacking to text, a second pass over the residual frame (the subtraction: cwslg_subtract_ft8), OSD
  * on AP-modified metrics. */
 typedef struct { uint8_t mask[12]; uint8_t value[12]; } cwslg_ap_pattern;   /* codeword bits 0..90, packed as cwslg_ft8_msg.bits */
 typedef struct { cwslg_ft8_msg msg; float dmin; } cwslg_ap_msg;             /* 24 bytes; msg.pad_ = pattern index, 0xff: none */
@@ -822,6 +824,92 @@ int cwslg_ap_decode(cwslg_ctx *ctx, const float *llr /* [n][174] */, int n, cwsl
  * an early stop across the three sets of a record. */
 int cwslg_set_ft4_ap(cwslg_ctx *ctx, const cwslg_ap_pattern *pat, int n_pat, int max_iter, int min_nsync, int min_nqual);
 int cwslg_fetch_ft4_ap(cwslg_ctx *ctx, uint64_t *start_epoch /* in/out */, cwslg_decode *dst, int max, int *n, int *n_total, int *n_channels);
+/* FT8 signal subtraction (PARITY UNPINNED like the rest of the chain): per decode of cwslg_fetch_decodes a refined frequency and start, fitted with
+ * the KNOWN word as the sync pattern (79 known symbols instead of 21 Costas symbols), and per channel a RESIDUAL frame: the float frame minus the
+ * fitted waveform of every emitted decode.  Everything it needs is on the device when the decodes are harvested -- the float frame, the
+ * re-encoder of the reports, the emitted records; without it a consumer pulls 720 KB per channel to the host and synthesises and fits there.
+ * Shaped like upstream's subtractft8 (reference waveform, complex amplitude low-passed, subtract), recalled and not copied, on grids of its own.
+ * A FETCH, not a stage: no record kind, no stamp, no launch at a boundary, no field in cwslg_stats, stats.sync_launches untouched; it never
+ * writes the frame, the plane, a list or a record.  tests/ft8_subtract_ref.py restates everything below in numpy, bit for bit.  Every float
+ * operation is one un-fused float32 operation in the order written; phases are uint32 arithmetic modulo 2^32, in units of 2^-32 turns.
+ *   Tables (cwsl_digi_amd/csrc/modules/ft8sub_tables.inc, written by scripts/gen_ft8sub_tables.py): CP[3][1920], CPT[3], COSQ[1025], WIN[97].
+ *   Waveform of (tones t[0..78] -- the reports' re-encoder --, increment inc): GFSK, BT = 2.0, unit amplitude, 79 x 1920 samples at 12 kHz.  Sample v
+ *       of symbol n has phase  base[n] + v inc + tp CP[2][v] + tc CP[1][v] + tn CP[0][v],  tp / tc / tn the tones of symbols n - 1 / n / n + 1
+ *       (n - 1 and n + 1 clamped to 0..78: the first and last tone are held outside the transmission); base[0] = 0, base[n + 1] = base[n] +
+ *       1920 inc + tp CPT[2] + tc CPT[1] + tn CPT[0].  CP[x][v] is the exclusive prefix of the per-sample integer increments of one tone unit
+ *       (6.25 Hz) of the pulse's third x, so the phase is the prefix of the increments  inc + tp P[2][v] + tc P[1][v] + tn P[0][v].
+ *       (cos, sin) = CS[(phase + 2^19) >> 20], CS[i] = (cos, sin)(2 pi i / 4096) made from the quarter-turn table by symmetry: cos is COSQ[r],
+ *       -COSQ[1024 - r], -COSQ[r], COSQ[1024 - r] in the four quarters (r = i mod 1024), sin(i) = cos(i - 1024).  No sinf / cosf anywhere.
+ *   Start: i0 = (int)clamp(rintf(dt_s * 12000.0f), -400000, 400000) + 6000 - 480; inc0 = (uint32)llrint((double)freq_hz * 2^32 / 12000).  The 480:
+ *       a candidate's dt_s is (time_step - 0.5) 0.04 s, while the window of plane step time_step + 12, where the search finds symbol 0, starts
+ *       0.04 time_step - 0.06 s after the protocol's 0.5 s: the signal's first sample lies one plane step BEFORE what dt_s names, and the time
+ *       search, half a step to either side, is centred there.  The report's dt_s is the signal's own start, so it is about 0.04 s below dec's.
+ *   Block sums of a start s and an increment: the signal's 151680 samples in 2528 blocks of 60 (32 per symbol); B[b] = (re, im), re = re + x c and
+ *       im = im - x s over the block's samples in ascending order from +0, x the frame sample (frame * conj(wave)); a sample before sample 0 or
+ *       past 179999 (or past the frame's n_valid: the zero tail) is +0, which leaves the sums as skipping it would.
+ *   Symbol metric of block sums: S[n] = the symbol's 32 block sums halved (a[l] = a[l] + a[l + h] for l < h, h = 16, 8, 4, 2, 1), per component;
+ *       M = sum over n = 0..78 ascending, from +0, of (S.re S.re + S.im S.im).
+ *   FIT, from the ORIGINAL frame for every decode (no decode sees another's subtraction; deterministic and parallel):
+ *     1. frequency, at block rate: B at (i0, inc0); for k = -52..52: B'[b] = (re cr + im sr, im cr - re sr), (cr, sr) = CS of the phase
+ *        (uint32)(k 11185) * (60 b + 30); the FIRST maximum of M over ascending k wins; inc = inc0 + k 11185.  The grid is 0.0312505 Hz wide
+ *        (11185 * 12000 / 2^32) and reaches +-1.62503 Hz: more than half a 3.125 Hz search bin.
+ *     2. time, at sample rate and at the refined frequency: for j = 0..60: M of the block sums at (i0 - 240 + 8 j, inc); the FIRST maximum over
+ *        ascending j wins; start = i0 - 240 + 8 j.  The grid is 8 samples (2/3 ms) wide and reaches +-240 samples: half a 40 ms plane step.
+ *     3. frequency once more, now that the symbols are aligned: step 1 on B at (start, inc), inc = inc + k2 11185 (df_steps = k + k2).
+ *        B at (start, inc); cnt[b] = samples of block b inside 0..179999.
+ *     4. amplitude track: a[b] = (sum_j WIN[j] B[b - 48 + j].re / den, the same of .im), den = sum_j WIN[j] (float)cnt[b - 48 + j], j = 0..96
+ *        ascending from +0, blocks outside 0..2527 contributing +0 -- a Hann window three symbols wide, normalised by the samples actually under
+ *        it, so the edges of the signal and of the frame are not pulled down; den > 0 else a[b] = +0.
+ *     5. figures, each summed as: thread l of 256 adds the terms of blocks l, l + 256, .. ascending from +0; then a[l] = a[l] + a[l + h] for l < h,
+ *        h = 128 .. 1.  p_removed: 2 (a.re a.re + a.im a.im) cnt (the energy of the fitted waveform, A cos carrying 2 |a|^2 per sample);
+ *        p_before: cnt > 0 ? 2 (B.re B.re + B.im B.im) / cnt : 0 -- the frame's energy along the signal's de-chirped track, 200 Hz wide around
+ *        the tone: its time-frequency footprint; p_after: the same of B - cnt a (this decode's own fit taken out, at block rate).
+ *   APPLY: residual[t] = frame[t] - sum over the channel's emitted decodes IN EMISSION ORDER of 2 y_d[t], i.e. r = r - 2.0f * y one decode after
+ *       the other in a register, no atomics; y = ar c - ai s at signal sample u = t - start (0 <= u < 151680, t inside the frame), (ar, ai) the
+ *       track between block centres: pp = 2 u - 59; pp < 0: a[0]; b0 = min(pp / 120, 2526), m = pp - 120 b0; m >= 120: a[2527]; otherwise
+ *       a[b0] + ((float)m * (1.0f / 120.0f)) * (a[b0 + 1] - a[b0]).
+ * 1. cwslg_subtract_ft8 is cwslg_fetch_decode_reports' contract for the FT8 group (points 1 to 7 of cwslg_fetch_decodes, one ticket, one
+ *    serialised call, the fetch stream, the group's staging blocks, a systematic code or CWSLG_ERR_ARG; dec byte-identical to cwslg_fetch_decodes
+ *    for that epoch and max; either output pointer may be null), with sub[p] the cwslg_subtract_report of dec[p].  The frame is the decoder's:
+ *    the first 180000 samples (15 s) of the channel's float frame, whose device buffer is the reference's 20 s.  Per channel that took part it
+ *    leaves the residual over the first min(n_total, max) records in a device block of the group, allocated by the first call, grown on demand,
+ *    freed by cwslg_destroy; a channel without an emitted decode -- and every channel at max = 0 -- gets the frame's own bits.  Two calls on one
+ *    epoch leave the same bytes.  Execution: descriptors up, the three harvest launches, the 16-byte head down and one synchronise (the fit
+ *    records, 20736 bytes each, are sized by what was emitted), ft8_sub_fit_kernel (one workgroup per emitted decode), ft8_sub_apply_kernel (one
+ *    workgroup per channel and 1024-sample tile), one copy down, one synchronise.  The kernels are in a code object of their own beside the
+ *    library (cwslgpu_ft8sub.hsaco), loaded by the first call; a missing file is CWSLG_ERR_ARG with a text that names it.
+ *    The call has no group argument: it is the FT8 group's.  FT4 channels never take part, and a context with FT4 channels alone answers
+ *    CWSLG_ERR_NO_FRAME like any call no channel takes part in; there is no FT4 subtraction to refuse with CWSLG_ERR_ARG.
+ *    The call holds the group's ticket for as long as it runs -- about 10 ms for 800 decodes against 0.2 ms for the report call -- and the
+ *    group's next boundary waits for the ticket with the context locked: a boundary that arrives during the call delays every push on the
+ *    context by the rest of it.  Call it right after the boundary, not just before the next one.
+ * 2. cwslg_fetch_ft8_residual copies a channel's residual (180000 floats, the units of cwslg_fetch_audio_f32; cap below that: CWSLG_ERR_ARG) and
+ *    cwslg_ft8_residual_device_ptr hands out its device address; both only while the residual's epoch is the channel's frame epoch, otherwise
+ *    CWSLG_ERR_NO_FRAME: never an older slot's residual under a newer epoch.  The next cwslg_subtract_ft8 overwrites the block, and FREES it
+ *    when more channels take part than it was sized for: an address handed out is dead from the next cwslg_subtract_ft8 call on.
+ * 3. cwslg_ft8_subtract_flat runs the same two kernels on caller-supplied frames (n_frames x 180000 floats) and items, the cwslg_ldpc_decode
+ *    pattern (synchronous, temporary device buffers, the context's stream): items in ascending frame order (else CWSLG_ERR_ARG), freq_hz in
+ *    0..6000 and |dt_s| <= 30, dt_s in the candidate's convention (a transmission that starts at T has dt_s = T + 0.04); sub[i] reports items[i]; residual, [n_frames][180000], may be null.  n_items = 0 gives residual = audio.
+ * Out of scope: a second search or decode pass over the residual, FT4, an int16 or prepareAudio-scaled residual, joint refitting of overlapping
+ * signals, unpacking to text. */
+typedef struct {
+    float   f_hz;        /* refined frequency of tone 0: inc * 12000 / 2^32 in double, rounded to float */
+    float   dt_s;        /* refined start: (float)(start - 6000) / 12000.0f */
+    float   p_removed;   /* energy of the fitted waveform, in squared units of cwslg_fetch_audio_f32 */
+    float   p_before;    /* the frame's energy in the signal's time-frequency footprint */
+    float   p_after;     /* the same with this decode's fit taken out */
+    int32_t n_inside;    /* samples of the 79 x 1920 inside the frame */
+    int16_t df_steps;    /* k + k2 of the two frequency searches, each -52..52 */
+    int16_t dt_steps;    /* j - 30 of the time grid, -30..30 */
+} cwslg_subtract_report;   /* 28 bytes */
+typedef struct { int32_t frame; uint8_t bits[12]; float freq_hz; float dt_s; } cwslg_ft8_sub_item;   /* 24 bytes; bits as cwslg_ft8_msg.bits */
+#define CWSLG_FT8_FRAME_SAMPLES 180000
+int cwslg_subtract_ft8(cwslg_ctx *ctx, uint64_t *start_epoch /* in/out */, cwslg_decode *dec, cwslg_subtract_report *sub, int max, int *n, int *n_total,
+                       int *n_channels);
+int cwslg_fetch_ft8_residual(cwslg_ctx *ctx, int ch_id, float *dst, size_t cap, size_t *n_valid, uint64_t *start_epoch);
+int cwslg_ft8_residual_device_ptr(cwslg_ctx *ctx, int ch_id, const float **d_f32, uint64_t *start_epoch);
+int cwslg_ft8_subtract_flat(cwslg_ctx *ctx, const float *audio /* [n_frames][180000] */, int n_frames, const cwslg_ft8_sub_item *items, int n_items,
+                            cwslg_subtract_report *sub, float *residual /* [n_frames][180000] or null */);
 int cwslg_fetch_slot(cwslg_ctx *ctx, int ch_id, int16_t *frame, size_t cap, void *list, size_t list_bytes,
                      cwslg_ft4_sync *ft4, int max_ft4, cwslg_slot_result *out);
 int cwslg_set_ft4_syncmin(cwslg_ctx *ctx, float syncmin);

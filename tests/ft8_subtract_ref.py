@@ -1,0 +1,272 @@
+"""numpy restatement of the FT8 subtractor (include/cwsl_gpu.h, "FT8 signal subtraction"): the contract's executable form.  Every float
+operation below is one un-fused float32 operation in the order written; the integer phase is uint32 arithmetic modulo 2^32.  No np.cos: the
+waveform comes from the committed tables (cwsl_digi_amd/csrc/modules/ft8sub_tables.inc, parsed here), so the device can agree on bits."""
+import os
+import re
+
+import numpy as np
+
+F32 = np.float32
+U32 = np.uint32
+HERE = os.path.dirname(os.path.abspath(__file__))
+TABLES_INC = os.path.join(HERE, "..", "cwsl_digi_amd", "csrc", "modules", "ft8sub_tables.inc")
+
+N = 180000                  # samples of a frame
+NSPS = 1920                 # samples of a symbol
+NSYM = 79
+NW = NSYM * NSPS            # samples of a signal
+BLK = 60                    # samples of a block
+BPS = NSPS // BLK           # 32 blocks per symbol
+NBLK = NSYM * BPS           # 2528
+TAU_MAX, TAU_STEP = 240, 8  # time grid: -240, -232 .. +240 samples (61 offsets of 2/3 ms)
+NTAU = 2 * TAU_MAX // TAU_STEP + 1
+DINC, KF = 11185, 52        # frequency grid: k * DINC * 12000 / 2^32 Hz, k = -52..52 (steps of 0.0312505 Hz, +-1.62503 Hz)
+NK = 2 * KF + 1
+HW = 48                     # half width of the track's window, in blocks
+CAND_STEP = 480             # a candidate's dt_s, (time_step - 0.5) 0.04 s, names the plane step AFTER the one whose window starts with the signal
+TIME_STEP_S = TAU_STEP / 12000.0
+FREQ_STEP_HZ = DINC * 12000.0 / 4294967296.0
+R120 = F32(1.0) / F32(120.0)
+
+SUB_DTYPE = np.dtype([("f_hz", F32), ("dt_s", F32), ("p_removed", F32), ("p_before", F32), ("p_after", F32), ("n_inside", np.int32),
+                      ("df_steps", np.int16), ("dt_steps", np.int16)])
+assert SUB_DTYPE.itemsize == 28
+
+
+def parse_tables(path=TABLES_INC):
+    text = open(path).read()
+    out = {}
+    for m in re.finditer(r"FT8SUB_TABLE (float|unsigned) (\w+)\[(\d+)\] = \{([^}]*)\};", text):
+        kind, name, count, body = m.group(1), m.group(2), int(m.group(3)), m.group(4)
+        toks = [t for t in body.replace("\n", " ").split(",") if t.strip()]
+        if kind == "float":
+            arr = np.array([float.fromhex(t.strip().rstrip("f")) for t in toks], np.float64).astype(F32)
+        else:
+            arr = np.array([int(t.strip(), 16) for t in toks], np.uint64).astype(U32)
+        assert arr.size == count, name
+        out[name] = arr
+    return out
+
+
+_T = parse_tables()
+CP = _T["FT8SUB_CP"].reshape(3, NSPS)
+CPT = _T["FT8SUB_CPT"]
+COSQ = _T["FT8SUB_COSQ"]
+WIN = _T["FT8SUB_WIN"]
+
+
+def _cos_of(idx):
+    """cos of 2 pi idx / 4096 from the quarter table: C[r], -C[1024 - r], -C[r], C[1024 - r] in the four quarters (r = idx mod 1024)"""
+    q, r = (idx >> 10) & 3, idx & 1023
+    v = np.where((q & 1) == 0, COSQ[r], COSQ[1024 - r])
+    return np.where((q == 1) | (q == 2), -v, v).astype(F32)
+
+
+def cos_sin(phase):
+    """(cos, sin) float32 of a uint32 phase (any integer array, taken modulo 2^32): the table index is the top 12 bits rounded to nearest;
+    sin(idx) = cos(idx - 1024)"""
+    idx = ((np.asarray(phase, np.int64) + 0x80000) & 0xffffffff) >> 20
+    return _cos_of(idx), _cos_of((idx - 1024) & 4095)
+
+
+def inc_of(f_hz):
+    """uint32 phase increment per sample of a float32 frequency: rint of the double product, modulo 2^32."""
+    return U32(int(np.rint(np.float64(F32(f_hz)) * (4294967296.0 / 12000.0))) & 0xffffffff)
+
+
+def start_of(dt_s):
+    """centre of the time search: rint(dt * 12000) in float32, clamped to +-400000, plus the protocol's 0.5 s, minus the one plane step by which a
+    candidate's dt_s lies after the signal's first sample"""
+    with np.errstate(all="ignore"):
+        v = float(np.rint(F32(dt_s) * F32(12000.0)))
+    if not v >= -400000.0:
+        v = -400000.0
+    if v > 400000.0:
+        v = 400000.0
+    return int(v) + 6000 - CAND_STEP
+
+
+def phase_bases(tones, inc):
+    """phase (uint32 turns) at the first sample of every symbol: what the increments of all symbols before add up to"""
+    t = np.asarray(tones, np.int64)
+    tp, tn = np.concatenate([t[:1], t[:-1]]), np.concatenate([t[1:], t[-1:]])
+    per = NSPS * int(inc) + tp * int(CPT[2]) + t * int(CPT[1]) + tn * int(CPT[0])
+    base = np.concatenate([[0], np.cumsum(per)[:-1]])
+    return (base & 0xffffffff).astype(U32)
+
+
+def wave(tones, inc):
+    """cos, sin (float32[NW]) of the unit waveform: integer phase, table by its top 12 bits rounded to nearest"""
+    t = np.asarray(tones, np.int64)
+    tp, tn = np.concatenate([t[:1], t[:-1]]), np.concatenate([t[1:], t[-1:]])
+    base = phase_bases(tones, inc).astype(np.int64)
+    v = np.arange(NSPS, dtype=np.int64)
+    ph = (base[:, None] + v[None, :] * int(inc) + tp[:, None] * CP[2].astype(np.int64)[None, :] + t[:, None] * CP[1].astype(np.int64)[None, :]
+          + tn[:, None] * CP[0].astype(np.int64)[None, :]) & 0xffffffff
+    return cos_sin(ph.reshape(-1))
+
+
+def _padded(frame, start, lo, hi):
+    """frame samples start+lo .. start+hi-1, +0 outside the frame"""
+    out = np.zeros(hi - lo, F32)
+    a, b = start + lo, start + hi
+    ca, cb = max(a, 0), min(b, N)
+    if cb > ca:
+        out[ca - a:cb - a] = frame[ca:cb]
+    return out
+
+
+def block_sums(x, c, s):
+    """x, c, s: float32[NW] -> (re, im) float32[NBLK]: re += x c, im -= x s over the block's 60 samples in ascending order"""
+    x, c, s = x.reshape(NBLK, BLK), c.reshape(NBLK, BLK), s.reshape(NBLK, BLK)
+    re, im = np.zeros(NBLK, F32), np.zeros(NBLK, F32)
+    for i in range(BLK):
+        re = re + x[:, i] * c[:, i]
+        im = im - x[:, i] * s[:, i]
+    return re, im
+
+
+def halve32(a):
+    """[..., 32] -> [...]: a[l] += a[l + h] for l < h, h = 16, 8, 4, 2, 1"""
+    for h in (16, 8, 4, 2, 1):
+        a = a[..., :h] + a[..., h:2 * h]
+    return a[..., 0]
+
+
+def symbol_metric(re, im):
+    """[..., NBLK] block sums -> sum over the 79 symbols, ascending, of |symbol sum|^2"""
+    sr, si = halve32(re.reshape(re.shape[:-1] + (NSYM, BPS))), halve32(im.reshape(im.shape[:-1] + (NSYM, BPS)))
+    p = sr * sr + si * si
+    m = np.zeros(p.shape[:-1], F32)
+    for n in range(NSYM):
+        m = m + p[..., n]
+    return m
+
+
+def first_max(m):
+    best, arg = m[0], 0
+    for i in range(1, len(m)):
+        if m[i] > best:
+            best, arg = m[i], i
+    return arg
+
+
+def tree256(terms):
+    """terms float32[NBLK] -> thread l adds terms l, l + 256, .. ascending; then a[l] += a[l + h], h = 128 .. 1"""
+    pad = np.zeros(10 * 256, F32)
+    pad[:NBLK] = terms
+    rows = pad.reshape(10, 256)
+    a = rows[0].copy()
+    for r in range(1, 10):
+        a = a + rows[r]
+    for h in (128, 64, 32, 16, 8, 4, 2, 1):
+        a = a[:h] + a[h:2 * h]
+    return a[0]
+
+
+def freq_search(re, im):
+    """index 0..104 of the first maximum over k = -52..52 of the symbol metric of the block sums turned back by k DINC (60 b + 30)"""
+    k = np.arange(-KF, KF + 1, dtype=np.int64)
+    u = 60 * np.arange(NBLK, dtype=np.int64) + 30
+    rho = (k[:, None] * DINC * u[None, :]) & 0xffffffff
+    cr, sr = cos_sin(rho)
+    rre = re[None, :] * cr + im[None, :] * sr
+    rim = im[None, :] * cr - re[None, :] * sr
+    return first_max(symbol_metric(rre, rim))
+
+
+def fit(frame, tones, freq_hz, dt_s):
+    """One decode against the ORIGINAL frame.  Returns (report record, fit dict with start, inc, tones, track a_re/a_im[NBLK])."""
+    frame = np.asarray(frame, F32)
+    inc0 = inc_of(freq_hz)
+    i0 = start_of(dt_s)
+    win = _padded(frame, i0, -TAU_MAX, NW + TAU_MAX)
+    # frequency search at block rate: the block sums at the candidate's time and frequency, turned back by k DINC (60 b + 30)
+    c, s = wave(tones, inc0)
+    ik = freq_search(*block_sums(win[TAU_MAX:TAU_MAX + NW], c, s))
+    inc = U32((int(inc0) + (ik - KF) * DINC) & 0xffffffff)
+    # time search at the refined frequency, at sample rate
+    c, s = wave(tones, inc)
+    m = np.zeros(NTAU, F32)
+    for it in range(NTAU):
+        re, im = block_sums(win[it * TAU_STEP:it * TAU_STEP + NW], c, s)
+        m[it] = symbol_metric(re, im)
+    it = first_max(m)
+    start = i0 - TAU_MAX + it * TAU_STEP
+    # the frequency search once more, now that the symbols are aligned, and the block sums at the winner
+    ik2 = freq_search(*block_sums(win[it * TAU_STEP:it * TAU_STEP + NW], c, s))
+    inc = U32((int(inc) + (ik2 - KF) * DINC) & 0xffffffff)
+    c, s = wave(tones, inc)
+    re, im = block_sums(win[it * TAU_STEP:it * TAU_STEP + NW], c, s)
+    t = start + np.arange(NW, dtype=np.int64)
+    cnt = ((t >= 0) & (t < N)).reshape(NBLK, BLK).sum(axis=1).astype(F32)
+    # amplitude track: Hann window over blocks b - 48 .. b + 48 inside the signal, ascending; normalised by the samples under the window
+    pre, pim, pc = (np.concatenate([np.zeros(HW, F32), v, np.zeros(HW, F32)]) for v in (re, im, cnt))
+    nre, nim, den = np.zeros(NBLK, F32), np.zeros(NBLK, F32), np.zeros(NBLK, F32)
+    for j in range(2 * HW + 1):
+        nre = nre + WIN[j] * pre[j:j + NBLK]
+        nim = nim + WIN[j] * pim[j:j + NBLK]
+        den = den + WIN[j] * pc[j:j + NBLK]
+    ok = den > 0
+    with np.errstate(all="ignore"):
+        a_re = np.where(ok, nre / np.where(ok, den, F32(1)), F32(0)).astype(F32)
+        a_im = np.where(ok, nim / np.where(ok, den, F32(1)), F32(0)).astype(F32)
+        # the figures, at block rate (energy of A cos = 2 |a|^2 per sample)
+        okc = cnt > 0
+        safe = np.where(okc, cnt, F32(1))
+        removed = tree256(F32(2.0) * (a_re * a_re + a_im * a_im) * cnt)
+        before = tree256(np.where(okc, F32(2.0) * (re * re + im * im) / safe, F32(0)).astype(F32))
+        dr, di = re - cnt * a_re, im - cnt * a_im
+        after = tree256(np.where(okc, F32(2.0) * (dr * dr + di * di) / safe, F32(0)).astype(F32))
+    rec = np.zeros((), SUB_DTYPE)
+    rec["f_hz"] = F32(np.float64(int(inc)) * (12000.0 / 4294967296.0))
+    rec["dt_s"] = F32(start - 6000) / F32(12000.0)
+    rec["p_removed"], rec["p_before"], rec["p_after"] = removed, before, after
+    rec["n_inside"] = int(cnt.sum())
+    rec["df_steps"], rec["dt_steps"] = (ik - KF) + (ik2 - KF), it - TAU_MAX // TAU_STEP
+    return rec, {"start": start, "inc": inc, "tones": np.asarray(tones, np.int64), "a_re": a_re, "a_im": a_im}
+
+
+def fitted_wave(f):
+    """float32[NW]: y = a_re c - a_im s, the track interpolated linearly between block centres (held flat before the first and after the last)"""
+    c, s = wave(f["tones"], f["inc"])
+    p = 2 * np.arange(NW, dtype=np.int64) - (BLK - 1)
+    b0 = np.clip(p // 120, 0, NBLK - 2)
+    m = p - 120 * b0
+    g = m.astype(F32) * R120
+    a0r, a1r, a0i, a1i = f["a_re"][b0], f["a_re"][b0 + 1], f["a_im"][b0], f["a_im"][b0 + 1]
+    with np.errstate(all="ignore"):
+        # before the first centre: a[0]; past the last: a[NBLK - 1]
+        ar = np.where(m >= 120, a1r, np.where(p < 0, a0r, a0r + g * (a1r - a0r))).astype(F32)
+        ai = np.where(m >= 120, a1i, np.where(p < 0, a0i, a0i + g * (a1i - a0i))).astype(F32)
+        return ar * c - ai * s
+
+
+def apply(frame, fits):
+    """residual = frame - 2 y_d for every fit in order, on the samples of the signal that lie inside the frame"""
+    out = np.array(frame, F32, copy=True)
+    for f in fits:
+        y = fitted_wave(f)
+        a, b = max(f["start"], 0), min(f["start"] + NW, N)
+        if b > a:
+            out[a:b] = out[a:b] - F32(2.0) * y[a - f["start"]:b - f["start"]]
+    return out
+
+
+def subtract(frame, items):
+    """items: (tones[79], freq_hz, dt_s) in emission order -> (reports SUB_DTYPE[n], residual float32[N], fits)"""
+    fits, recs = [], np.zeros(len(items), SUB_DTYPE)
+    for i, (tones, f, dt) in enumerate(items):
+        recs[i], ft = fit(frame, tones, f, dt)
+        fits.append(ft)
+    return recs, apply(frame, fits), fits
+
+
+def footprint_power(frame, f):
+    """test-side measure: the energy of ANY frame along a fit's de-chirped track (what p_before is for the original frame)"""
+    c, s = wave(f["tones"], f["inc"])
+    re, im = block_sums(_padded(np.asarray(frame, F32), f["start"], 0, NW), c, s)
+    t = f["start"] + np.arange(NW, dtype=np.int64)
+    cnt = ((t >= 0) & (t < N)).reshape(NBLK, BLK).sum(axis=1).astype(np.float64)
+    e = 2.0 * (re.astype(np.float64) ** 2 + im.astype(np.float64) ** 2)
+    return float(np.sum(e[cnt > 0] / cnt[cnt > 0]))

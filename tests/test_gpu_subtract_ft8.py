@@ -1,0 +1,220 @@
+"""GPU: cwslg_subtract_ft8 on the chain (include/cwsl_gpu.h, "FT8 signal subtraction") -- 3 channels x 1 slot, the smallest group that has a channel
+with several decodes, one with one and one with none.  Every comparison is byte for byte: `dec` against cwslg_fetch_decodes, `sub` and every
+residual against tests/ft8_subtract_ref.py applied to the GPU's own float frame (cwslg_fetch_audio_f32) and `dec`."""
+import ctypes as C
+import functools
+
+import numpy as np
+import pytest
+
+import decode_reports_ref as RR
+import ft8_subtract_ref as S
+import ldpc_cases as LC
+import osd_cases as OC
+import record_race_cases as RC
+import report_kernel_cases as K
+
+pytestmark = pytest.mark.gpu
+NO_FRAME, ERR_ARG = -9, -6
+BIG = 1 << 16
+MODE = "FT8"
+SEED = RC.SEED
+# The slot is osd_cases' chain slot (eight transmissions on three dial offsets, all decoded by BP or OSD under this seed).  Dial offsets here: its
+# first channel (three transmissions: several decodes); its second one 1500 Hz lower, which puts one transmission at 2218.75 Hz and the other
+# above the search band (one decode); noise alone, whose list is empty at this syncmin (none)
+RFS = (OC.CHAIN[0][0], OC.CHAIN[1][0] - 1500, OC.QUIET_RF)
+E0 = RC.start_epoch(MODE, 0)
+
+
+def _open(ctx, seed=SEED, code=None):
+    s = RC.SYNC
+    ctx.enable_sync(True, OC.QUIET_SYNCMIN, 100, s["f_lo"], s["f_hi"])
+    ctx.set_ldpc_code(LC.make_code(seed)["nm"] if code is None else code)
+    ctx.enable_ft8_softbits(True)
+    ctx.enable_ft8_decode(True, *RC.DECODE8)
+    ctx.enable_ft8_osd(True, *RC.OSD8)
+    rx = ctx.receiver_open(RC.FS, RC.BLK[MODE], 0)
+    chans = [ctx.channel_open(rx, rf, MODE) for rf in RFS]
+    ctx.slot_boundary(MODE, E0)
+    return rx, chans
+
+
+def _slot(ctx, rx, e):
+    iq, step = OC.chain_iq(SEED), 64 * RC.BLK[MODE]                      # (every slot carries the same IQ: the epochs differ, which is what matters here)
+    for k in range(0, len(iq), step):
+        ctx.push_iq(rx, iq[k:k + step])
+    ctx.slot_boundary(MODE, RC.start_epoch(MODE, e + 1))
+
+
+@pytest.fixture(scope="module")
+def slot():
+    """(ctx, chans) with slot 0 decoded; the tests below only fetch, except the last one of the file, which fires the next boundary"""
+    import cwsl_digi_amd as P
+    c = P.Context(0)
+    rx, chans = _open(c)
+    _slot(c, rx, 0)
+    yield c, rx, chans
+    c.close()
+
+
+_REF = {}
+
+
+def _want(ctx, chans, dec, key):
+    """the restatement on the GPU's own frames and `dec`: (sub, {ch: residual}); computed once per (frame set, max) and shared"""
+    if key in _REF:
+        return _REF[key]
+    G = K.encoder(SEED)
+    sub = np.zeros(len(dec), S.SUB_DTYPE)
+    res = {}
+    for ch in chans:
+        audio, nv = ctx.fetch_audio_f32(ch)             # (the reference's 20 s buffer: the decoder's frame is its first 15 s)
+        assert audio.size >= S.N and not audio[nv:].any()
+        audio = audio[:S.N]
+        idx = np.flatnonzero(dec["ch_id"] == ch)
+        recs, res[ch], _ = S.subtract(audio, [(RR.tones(G, dec["bits"][i]), dec["freq_hz"][i], dec["dt_s"][i]) for i in idx])
+        sub[idx] = recs
+    _REF[key] = (sub, res)
+    return _REF[key]
+
+
+def _check(ctx, chans, mx, key):
+    plain = ctx.fetch_decodes(MODE, 0, mx)
+    got = ctx.subtract_ft8(0, mx)
+    dec, sub, E, n_total, n_ch = got
+    assert (E, n_total, n_ch) == plain[1:] and dec.tobytes() == plain[0].tobytes() and len(sub) == len(dec) == min(n_total, mx)
+    want_sub, want_res = _want(ctx, chans, dec, key)
+    bad = [p for p in range(len(dec)) if sub[p].tobytes() != want_sub[p].tobytes()]
+    assert not bad, (bad[:5], sub[bad[:3]], want_sub[bad[:3]])
+    for ch in chans:
+        r, e = ctx.fetch_ft8_residual(ch)
+        assert e == E
+        diff = np.flatnonzero(r.view(np.uint32) != want_res[ch].view(np.uint32))
+        assert diff.size == 0, (ch, diff.size, diff[:5])
+    return got
+
+
+def test_slot_against_the_restatement(slot):
+    ctx, rx, chans = slot
+    dec, sub, E, n_total, n_ch = _check(ctx, chans, BIG, "exact-all")
+    assert (E, n_ch) == (E0, 3)
+    counts = [int((dec["ch_id"] == ch).sum()) for ch in chans]
+    print("decodes per channel:", counts)
+    assert counts[0] >= 2 and counts[1] == 1 and counts[2] == 0, counts          # several, one, none
+    # the channel without a decode: the frame's own bits
+    audio, _ = ctx.fetch_audio_f32(chans[2])
+    assert ctx.fetch_ft8_residual(chans[2])[0].tobytes() == audio[:S.N].tobytes()
+    # the device address is handed out under the same rule
+    p, e = ctx.ft8_residual_device_ptr(chans[0])
+    assert p and e == E
+    # two calls on one epoch: the same bytes, reports and residuals
+    res = [ctx.fetch_ft8_residual(ch)[0].tobytes() for ch in chans]
+    again = ctx.subtract_ft8(E, BIG)
+    assert again[0].tobytes() == dec.tobytes() and again[1].tobytes() == sub.tobytes() and again[2:] == (E, n_total, n_ch)
+    assert [ctx.fetch_ft8_residual(ch)[0].tobytes() for ch in chans] == res
+
+
+def test_truncation_by_max_and_null_outputs(slot):
+    ctx, rx, chans = slot
+    full = ctx.subtract_ft8(0, BIG)
+    n_total = full[3]
+    assert n_total >= 3
+    # max = 0: nothing emitted, every residual is the frame; max = 1: the first decode alone is taken out; max beyond n_total: all of them
+    got = ctx.subtract_ft8(0, 0)
+    assert len(got[0]) == 0 and got[3] == n_total
+    for ch in chans:
+        assert ctx.fetch_ft8_residual(ch)[0].tobytes() == ctx.fetch_audio_f32(ch)[0][:S.N].tobytes()
+    _check(ctx, chans, 1, "exact-1")
+    _check(ctx, chans, n_total + 1, "exact-all")
+    # null dec / null sub: the counts are the same, nothing is written through the null pointer, the residual is made all the same
+    for null_dec, null_sub in ((True, False), (False, True), (True, True)):
+        dec, sub = np.zeros(n_total, full[0].dtype), np.zeros(n_total, full[1].dtype)
+        t0, n, nt, nc = C.c_uint64(0), C.c_int(-1), C.c_int(-1), C.c_int(-1)
+        rc = ctx.L.cwslg_subtract_ft8(ctx.h, C.byref(t0), None if null_dec else dec.ctypes.data, None if null_sub else sub.ctypes.data, n_total,
+                                      C.byref(n), C.byref(nt), C.byref(nc))
+        assert (rc, t0.value, n.value, nt.value, nc.value) == (0, E0, n_total, n_total, 3)
+        assert null_dec or dec.tobytes() == full[0].tobytes()
+        assert null_sub or sub.tobytes() == full[1].tobytes()
+        want = _REF["exact-all"][1]
+        assert all(ctx.fetch_ft8_residual(ch)[0].tobytes() == want[ch].tobytes() for ch in chans)
+
+
+def test_the_call_changes_nothing_else(slot):
+    ctx, rx, chans = slot
+
+    def state():
+        out = [repr(sorted(ctx.stats().items()))]
+        for ch in chans:
+            out += [ctx.fetch_audio_f32(ch)[0].tobytes(), ctx.sync_debug(ch, "spectra").tobytes(), repr(ctx.fetch_candidates(ch, 600)),
+                    ctx.fetch_ft8_softbits(ch, 600)[0].tobytes(), ctx.fetch_ft8_decode(ch, 600).tobytes(), ctx.fetch_ft8_osd(ch, 600).tobytes(),
+                    ctx.fetch_frame(ch)["i16"].tobytes()]
+        return out
+    before = state()
+    sync_launches = ctx.stats()["sync_launches"]
+    ctx.subtract_ft8(0, BIG)
+    ctx.subtract_ft8(0, 1)
+    assert ctx.stats()["sync_launches"] == sync_launches
+    assert state() == before
+
+
+def test_error_paths(slot):
+    import cwsl_digi_amd as P
+    ctx, rx, chans = slot
+    t0, n, nt = C.c_uint64(0), C.c_int(-1), C.c_int(-1)
+    assert ctx.L.cwslg_subtract_ft8(ctx.h, None, None, None, 0, C.byref(n), C.byref(nt), None) == ERR_ARG
+    assert ctx.L.cwslg_subtract_ft8(ctx.h, C.byref(t0), None, None, 0, None, C.byref(nt), None) == ERR_ARG
+    assert ctx.subtract_ft8(E0 + 15, BIG) is None                       # no channel has that epoch
+    with pytest.raises(P.CwslGpuError) as e:
+        ctx.fetch_ft8_residual(99)
+    assert e.value.status == ERR_ARG
+    out = np.zeros(10, np.float32)
+    assert ctx.L.cwslg_fetch_ft8_residual(ctx.h, chans[0], out.ctypes.data, out.size, None, None) == ERR_ARG      # destination too small
+    # a table without systematic form: decodes as before, no subtraction
+    with P.Context(0) as c2:
+        rx2, ch2 = _open(c2, code=K.singular_table(SEED))
+        _slot(c2, rx2, 0)
+        assert c2.fetch_decodes(MODE) is not None
+        with pytest.raises(P.CwslGpuError) as e:
+            c2.subtract_ft8()
+        assert e.value.status == ERR_ARG and "systematic" in str(e.value)
+        assert c2.fetch_ft8_residual(ch2[0]) is None
+
+
+def test_ft4_group_has_no_subtraction():
+    """the FT4 group: the call is the FT8 group's by its signature; an FT4 channel's id has no residual, and a context with FT4 channels alone has
+    no FT8 channel that takes part"""
+    import cwsl_digi_amd as P
+    with P.Context(0) as c:
+        c.set_ldpc_code(LC.make_code(SEED)["nm"])
+        rx = c.receiver_open(RC.FS, RC.BLK["FT4"], 0)
+        ch = c.channel_open(rx, RC.RF["FT4"][0], "FT4")
+        c.slot_boundary("FT4", RC.start_epoch("FT4", 0))
+        assert c.subtract_ft8() is None
+        assert c.fetch_ft8_residual(ch) is None
+
+
+def test_fast_mode_frame():
+    """cwslg_set_exact(ctx, 0): the fused polyphase frame differs from the exact one in its last bits; the subtractor works on the frame that is
+    there, and the same equality holds"""
+    import cwsl_digi_amd as P
+    with P.Context(0) as c:
+        c.set_exact(False)
+        rx, chans = _open(c)
+        _slot(c, rx, 0)
+        got = _check(c, chans, BIG, "fast-all")
+        assert got[3] >= 1
+
+
+def test_residual_is_gone_after_the_next_boundary(slot):
+    """(the last test on the shared context: it moves the group on)"""
+    ctx, rx, chans = slot
+    ctx.subtract_ft8(0, BIG)
+    assert ctx.fetch_ft8_residual(chans[0]) is not None
+    _slot(ctx, rx, 1)                                                   # the frames are now of the next epoch; the block still holds slot 0
+    for ch in chans:
+        assert ctx.fetch_ft8_residual(ch) is None and ctx.ft8_residual_device_ptr(ch) is None
+    t0 = C.c_uint64()
+    out = np.zeros(S.N, np.float32)
+    assert ctx.L.cwslg_fetch_ft8_residual(ctx.h, chans[0], out.ctypes.data, out.size, None, C.byref(t0)) == NO_FRAME and not out.any()
+    got = ctx.subtract_ft8(0, BIG)                                      # the new slot: residuals again, of its epoch
+    assert got[2] == RC.start_epoch(MODE, 1) and ctx.fetch_ft8_residual(chans[0])[1] == got[2]
