@@ -193,6 +193,9 @@ SUBTRACT_REPORT_DTYPE = np.dtype([("f_hz", np.float32), ("dt_s", np.float32), ("
                                   ("n_inside", np.int32), ("df_steps", np.int16), ("dt_steps", np.int16)])
 FT8_SUB_ITEM_DTYPE = np.dtype([("frame", np.int32), ("bits", np.uint8, 12), ("freq_hz", np.float32), ("dt_s", np.float32)])
 assert SUBTRACT_REPORT_DTYPE.itemsize == 28 and FT8_SUB_ITEM_DTYPE.itemsize == 24
+# cwslg_ft4_sub_item, the input of cwslg_ft4_subtract_flat: the FT8 item's layout (freq_hz: a record's f1_hz); a frame is the decoder's 72576 samples
+FT4_SUB_ITEM_DTYPE = np.dtype(FT8_SUB_ITEM_DTYPE.descr)
+FT4_FRAME_SAMPLES = 72576
 FT8_FRAME_SAMPLES = 180000
 
 
@@ -247,6 +250,7 @@ ABI_SYMBOLS = [
     "cwslg_fetch_decode_reports", "cwslg_ft8_tones", "cwslg_fetch_ft4_decode_reports", "cwslg_ft4_tones",
     "cwslg_set_ft8_ap", "cwslg_fetch_ft8_ap", "cwslg_ap_decode", "cwslg_set_ft4_ap", "cwslg_fetch_ft4_ap",
     "cwslg_subtract_ft8", "cwslg_fetch_ft8_residual", "cwslg_ft8_residual_device_ptr", "cwslg_ft8_subtract_flat",
+    "cwslg_subtract_ft4", "cwslg_fetch_ft4_residual", "cwslg_ft4_residual_device_ptr", "cwslg_ft4_subtract_flat",
     "cwslg_set_timing", "cwslg_demod_kernel_name", "cwslg_stream", "cwslg_channel_constants", "cwslg_phasor_checkpoint_stride", "cwslg_channel_phasor_checkpoints",
     "cwslg_slot_clock_next", "cwslg_pool_sizing", "cwslg_find_band", "cwslg_parse_decode_line",
     "cwslg_decoder_block_bytes", "cwslg_decoder_block_field", "cwslg_fill_decoder_block", "cwslg_decoder_route", "cwslg_decoder_command",
@@ -354,6 +358,10 @@ def load_library(build_if_missing=True):
     L.cwslg_fetch_ft8_residual.argtypes = [vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(u64)]
     L.cwslg_ft8_residual_device_ptr.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(u64)]
     L.cwslg_ft8_subtract_flat.argtypes = [vp, vp, i32, vp, i32, vp, vp]
+    L.cwslg_subtract_ft4.argtypes = [vp, C.POINTER(u64), vp, vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
+    L.cwslg_fetch_ft4_residual.argtypes = [vp, i32, vp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(u64)]
+    L.cwslg_ft4_residual_device_ptr.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(u64)]
+    L.cwslg_ft4_subtract_flat.argtypes = [vp, vp, i32, vp, i32, vp, vp]
     L.cwslg_fetch_ft4_decode_reports.argtypes = [vp, C.POINTER(u64), vp, vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     L.cwslg_ft4_tones.argtypes = [vp, vp, vp]
     L.cwslg_set_ft8_ap.argtypes = [vp, vp, i32, i32, i32]
@@ -938,6 +946,56 @@ class Context:
         sub = np.zeros(max(it.size, 1), SUBTRACT_REPORT_DTYPE)
         res = np.zeros_like(a) if want_residual else None
         self._chk(self.L.cwslg_ft8_subtract_flat(self.h, a.ctypes.data, a.shape[0], it.ctypes.data if it.size else None, it.size,
+                                                 sub.ctypes.data if it.size else None, res.ctypes.data if want_residual else None))
+        return sub[:it.size].copy(), res
+
+    def subtract_ft4(self, start_epoch=0, max=4096):
+        """cwslg_subtract_ft4: fetch_decodes("FT4") with a refined fit per decode, and a residual frame left on the device for every FT4 channel
+        that took part (fetch_ft4_residual).  Needs a systematic code loaded.  -> None if no channel takes part, else (records, sub, start_epoch,
+        n_total, n_channels), as subtract_ft8."""
+        m = int(max)
+        dec, sub = np.zeros(m if m > 1 else 1, DECODE_DTYPE), np.zeros(m if m > 1 else 1, SUBTRACT_REPORT_DTYPE)
+        t0, n, n_total, n_ch = C.c_uint64(int(start_epoch)), C.c_int(), C.c_int(), C.c_int()
+        rc = self.L.cwslg_subtract_ft4(self.h, C.byref(t0), dec.ctypes.data if m > 0 else None, sub.ctypes.data if m > 0 else None, m,
+                                       C.byref(n), C.byref(n_total), C.byref(n_ch))
+        if rc == ERR_NO_FRAME:
+            return None
+        self._chk(rc)
+        return dec[:n.value].copy(), sub[:n.value].copy(), t0.value, n_total.value, n_ch.value
+
+    def fetch_ft4_residual(self, ch):
+        """cwslg_fetch_ft4_residual: the channel's residual frame of the last subtract_ft4 -> (float32[72576], start_epoch), or None once the
+        channel's frame is of another epoch (or the channel did not take part, or is no FT4 channel)."""
+        out = np.zeros(FT4_FRAME_SAMPLES, np.float32)
+        nv, t0 = C.c_size_t(), C.c_uint64()
+        rc = self.L.cwslg_fetch_ft4_residual(self.h, int(ch), out.ctypes.data, out.size, C.byref(nv), C.byref(t0))
+        if rc == ERR_NO_FRAME:
+            return None
+        self._chk(rc)
+        return out, t0.value
+
+    def ft4_residual_device_ptr(self, ch):
+        """cwslg_ft4_residual_device_ptr -> (device address of the channel's residual, start_epoch), or None (as fetch_ft4_residual)."""
+        p, t0 = C.c_void_p(), C.c_uint64()
+        rc = self.L.cwslg_ft4_residual_device_ptr(self.h, int(ch), C.byref(p), C.byref(t0))
+        if rc == ERR_NO_FRAME:
+            return None
+        self._chk(rc)
+        return p.value, t0.value
+
+    def ft4_subtract_flat(self, audio, items, want_residual=True):
+        """cwslg_ft4_subtract_flat: the FT4 subtractor's two kernels on caller-supplied frames.  audio: float32 [n_frames][72576]; items: an array
+        of FT4_SUB_ITEM_DTYPE (or tuples (frame, bits[12], f1_hz, dt_s)) in ascending frame order.  -> (sub SUBTRACT_REPORT_DTYPE[n_items],
+        residual float32 [n_frames][72576] or None)."""
+        a = np.ascontiguousarray(audio, np.float32)
+        if a.ndim == 1:
+            a = a.reshape(1, -1)
+        if a.ndim != 2 or a.shape[1] != FT4_FRAME_SAMPLES:
+            raise ValueError("audio: [n_frames][72576]")
+        it = np.ascontiguousarray(np.asarray(items, FT4_SUB_ITEM_DTYPE).reshape(-1))
+        sub = np.zeros(max(it.size, 1), SUBTRACT_REPORT_DTYPE)
+        res = np.zeros_like(a) if want_residual else None
+        self._chk(self.L.cwslg_ft4_subtract_flat(self.h, a.ctypes.data, a.shape[0], it.ctypes.data if it.size else None, it.size,
                                                  sub.ctypes.data if it.size else None, res.ctypes.data if want_residual else None))
         return sub[:it.size].copy(), res
 

@@ -18,7 +18,9 @@ LAB_LIB = os.path.join(LIBDIR, "libcwslgpu_lab.so")
 # first call that subtracts.  Its sources live in csrc/modules/, which sources() does not compile into the libraries.
 MODDIR = os.path.join(CSRC, "modules")
 FT8SUB_MODULE = os.path.join(LIBDIR, "cwslgpu_ft8sub.hsaco")
-MODULES = ((FT8SUB_MODULE, os.path.join(MODDIR, "ft8sub.hip")),)
+# the FT4 subtractor's: a third code object, for the same reason
+FT4SUB_MODULE = os.path.join(LIBDIR, "cwslgpu_ft4sub.hsaco")
+MODULES = ((FT8SUB_MODULE, os.path.join(MODDIR, "ft8sub.hip")), (FT4SUB_MODULE, os.path.join(MODDIR, "ft4sub.hip")))
 BINDIR = os.path.join(HERE, "bin")
 # (CWSLG_SKIMMER_BIN / CWSLG_REALTIME_BIN: other builds of the two host programs for the tests that drive them -- the ThreadSanitizer builds of
 # scripts/gpu_r5_tsan.sh; test tooling only, the programs themselves read no such variable)

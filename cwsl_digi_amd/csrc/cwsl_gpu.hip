@@ -55,6 +55,7 @@
 #include "harvest_kernels.hpp"
 #include "ap_kernels.hpp"
 #include "ft8sub_layout.hpp"
+#include "ft4sub_layout.hpp"
 
 namespace cwslg {
 
@@ -236,6 +237,8 @@ struct HarvestStage {
 // The FT8 subtractor (cwslg_subtract_ft8, cwslg_ft8_subtract_flat; ft8sub_host.inc): the code object with its two kernels, loaded by the first
 // call that needs it, the per-decode fit records and the FT8 group's residual block.  A context that never subtracts loads and
 // holds nothing.  The module handles are guarded by the context mutex; the blocks by harvest[0].mu, which serialises the group's calls.
+// The FT4 subtractor (cwslg_subtract_ft4, cwslg_ft4_subtract_flat) is a second stage of the same shape: its own code object, fit
+// records (F4SUB_REC_WORDS) and residual block ([channels][72576]), the blocks guarded by harvest[1].mu.
 struct Ft8SubStage {
     hipModule_t module = nullptr;
     hipFunction_t fit = nullptr, apply = nullptr;
@@ -340,7 +343,7 @@ struct cwslg_ctx {
     LongConfig long_cfg;
     LongShared long_shared;
     HarvestStage harvest[2];           // cwslg_fetch_decodes: [0] the FT8 group's, [1] the FT4 group's
-    Ft8SubStage ft8sub;
+    Ft8SubStage ft8sub, ft4sub;
     std::mutex report_mu;              // the report calls of BOTH groups, one at a time: they share the encoder's device copy (taken after harvest[].mu, before mu)
     // side stream: optionally (CWSLG_SYNC_VARIANT bit 3) carries the FT8 candidate kernel next to the following demod launch
     hipStream_t side = nullptr;
@@ -1289,9 +1292,11 @@ void cwslg_destroy(cwslg_ctx *c)
         if (hs.d) (void)hipFree(hs.d);
         if (hs.d_ap) (void)hipFree(hs.d_ap);
     }
-    if (c->ft8sub.d_recs) (void)hipFree(c->ft8sub.d_recs);
-    if (c->ft8sub.d_resid) (void)hipFree(c->ft8sub.d_resid);
-    if (c->ft8sub.module) (void)hipModuleUnload(c->ft8sub.module);
+    for (Ft8SubStage *st : {&c->ft8sub, &c->ft4sub}) {
+        if (st->d_recs) (void)hipFree(st->d_recs);
+        if (st->d_resid) (void)hipFree(st->d_resid);
+        if (st->module) (void)hipModuleUnload(st->module);
+    }
     if (c->clk_h) (void)hipHostFree(c->clk_h);
     for (hipStream_t fs : c->fetch_stream) if (fs) { (void)hipStreamSynchronize(fs); (void)hipStreamDestroy(fs); }
     for (hipEvent_t e : c->fetch_ev) if (e) (void)hipEventDestroy(e);

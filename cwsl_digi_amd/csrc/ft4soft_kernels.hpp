@@ -27,7 +27,8 @@
 
 #include "ft4sync_kernels.hpp"
 #include "ft8soft_kernels.hpp"
-#include "harvest_kernels.hpp"      // the record layout ft4_report_kernel reads, report_pick6, REPORT_*
+#include "harvest_kernels.hpp"      // the record layout ft4_report_kernel reads, REPORT_*
+#include "ft4_tone_device.hpp"      // FT4S_ICOS4, ft4s_gray, ft4r_tone
 
 namespace cwslg {
 
@@ -35,12 +36,10 @@ constexpr int FT4S_NN = 103, FT4S_NBM = 206, FT4S_NBIT = 174;
 struct Ft4SoftRec { float llr[3][FT4S_NBIT]; float sigma[3]; int32_t nsync, nqual, pad_; };       // = cwslg_ft4_soft
 static_assert(sizeof(Ft4SoftRec) == 2112, "cwslg_ft4_soft is 2112 bytes");
 
-// icos4 (0132 1023 2310 3201), two bits per entry [4 b + s]; the four hard-decision patterns of nqual, one bit per entry [8 block + j]
-constexpr unsigned ft4s_pack2(const int (&v)[16]) { unsigned c = 0; for (int i = 0; i < 16; ++i) c |= (unsigned)v[i] << (2 * i); return c; }
+// (icos4, FT4S_ICOS4: ft4_tone_device.hpp)  the four hard-decision patterns of nqual, one bit per entry [8 block + j]
 constexpr unsigned ft4s_pack1(const int (&v)[32]) { unsigned c = 0; for (int i = 0; i < 32; ++i) c |= (unsigned)v[i] << i; return c; }
-constexpr int FT4S_ICOS4_V[16] = {0, 1, 3, 2, 1, 0, 2, 3, 2, 3, 1, 0, 3, 2, 0, 1};
 constexpr int FT4S_QUAL_V[32] = {0, 0, 0, 1, 1, 0, 1, 1, 0, 1, 0, 0, 1, 1, 1, 0, 1, 1, 1, 0, 0, 1, 0, 0, 1, 0, 1, 1, 0, 0, 0, 1};
-constexpr unsigned FT4S_ICOS4 = ft4s_pack2(FT4S_ICOS4_V), FT4S_QUAL = ft4s_pack1(FT4S_QUAL_V);
+constexpr unsigned FT4S_QUAL = ft4s_pack1(FT4S_QUAL_V);
 
 // ---- the decode reports (cwslg_fetch_ft4_decode_reports; the contract is the header's, tests/ft4_decode_reports_ref.py restates it) ----
 // One channel that takes part in a report call, in an array of its own beside the HarvestDesc array (same index).
@@ -64,7 +63,6 @@ struct Ft4ReportArgs {
 
 __device__ __forceinline__ float ft4s_mag(float2 z) { return sqrtf(__builtin_fmaf(z.x, z.x, z.y * z.y)); }
 __device__ __forceinline__ float2 ft4s_add(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ int ft4s_gray(int v) { return v ^ (v >> 1); }                           // graymap 0,1,3,2
 
 // The first two thirds of a record's work, ONE text for the soft bits and for the decode reports: the baseband at f1 from the channel's frame
 // spectrum cx, then the 412 symbol-spectrum chains -> s_cs[103][4] and their magnitudes s_mag[103][4].  Called by all 256 threads; ends behind
@@ -99,18 +97,7 @@ __device__ __forceinline__ void ft4s_symbol_spectra(const F4BaseLds &L, const fl
 }
 
 // ---- ft4_report_kernel: the FT4 decode reports (cwslg_fetch_ft4_decode_reports) -----------------------------------------------------------------------
-// the tone of symbol n (0..102) of the codeword c0..c5 (OsdGen bit layout); *costas: n is a Costas symbol
-__device__ __forceinline__ int ft4r_tone(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned c4, unsigned c5, int n, bool *costas)
-{
-    const int blk = n < 33 ? 0 : n < 66 ? 1 : n < 99 ? 2 : 3, r = n - 33 * blk;
-    *costas = r < 4;
-    const int icos = (int)((FT4S_ICOS4 >> (2 * (4 * blk + (r < 4 ? r : 0)))) & 3u);
-    const int d = n - 4 * (blk + 1);                                    // data symbol 0..86 (meaningless for a Costas symbol: clamped)
-    const int t = 2 * (d < 0 ? 0 : d > 86 ? 86 : d);                    // even: cw[2d], cw[2d+1] lie in one word
-    const unsigned x = report_pick6(c0, c1, c2, c3, c4, c5, t >> 5) >> (t & 31) & 3u;      // cw[2d] | cw[2d+1] << 1
-    const int v = (int)((x & 1u) << 1 | x >> 1);
-    return r < 4 ? icos : ft4s_gray(v);
-}
+// (ft4r_tone: ft4_tone_device.hpp)
 
 // One symbol: is the first maximum of the magnitudes at the encoded tone?  the power at the tone and at the tone two bins away
 __device__ __forceinline__ bool ft4r_symbol(const float2 (*s_cs)[4], const float (*s_mag)[4], int n, int tone, float *sig, float *noi)

@@ -1002,7 +1002,7 @@ int cwslg_fetch_ft4_osd(cwslg_ctx *c, int ch_id, cwslg_ft4_osd *dst, int max, in
 // a-priori (cwslg_fetch_ft8_ap, cwslg_fetch_ft4_ap; ap_kernels.hpp): an ApDesc per channel, the pattern block and the tables of the code in force go up
 // behind the HarvestDesc array in the same copy; the a-priori decode (ap_decode_kernel) runs IN FRONT of the three harvest launches and leaves a decode-record array
 // per channel in the group's AP staging, which is what HarvestDesc.msg then points at (.osd null); one annotate launch follows them.
-// subtraction (cwslg_subtract_ft8; ft8sub_host.inc, modules/ft8sub.hip): a SubDesc per channel goes up like the ReportDesc, the head comes down behind
+// subtraction (cwslg_subtract_ft8, cwslg_subtract_ft4; ft8sub_host.inc, modules/ft8sub.hip, modules/ft4sub.hip): a SubDesc per channel goes up like the ReportDesc, the head comes down behind
 // the harvest launches (the fit records are sized by what was emitted), the module's fit and apply launches follow, and the 28-byte reports come
 // down behind the records in the same copy; the residuals stay on the device, in the group's block.
 enum { FETCH_DECODES = 0, FETCH_REPORTS = 1, FETCH_AP = 2, FETCH_SUBTRACT = 3 };
@@ -1015,6 +1015,9 @@ static int fetch_decodes_impl(cwslg_ctx *c, int group, uint64_t *start_epoch, cw
     const size_t rep_words = subtract ? F8SUB_REP_WORDS : REPORT_WORDS;
     std::vector<SubDesc> sdescs;
     std::vector<int> sub_chans;
+    // (subtract: the group's own stage, frame length, fit record and tiling -- FT8 180000 samples, FT4 the decoder's first 72576)
+    Ft8SubStage &sub_stage = group == CWSLG_GROUP_FT4 ? c->ft4sub : c->ft8sub;
+    const size_t sub_n = group == CWSLG_GROUP_FT4 ? F4SUB_N : F8SUB_N, sub_rec_words = group == CWSLG_GROUP_FT4 ? F4SUB_REC_WORDS : F8SUB_REC_WORDS;
     static_assert(sizeof(cwslg_decode) == HARVEST_REC_WORDS * sizeof(unsigned), "record layout");
     static_assert(sizeof(cwslg_decode_report) == sizeof(ReportRec), "record layout");
     const bool ft4 = group == CWSLG_GROUP_FT4;
@@ -1043,7 +1046,7 @@ static int fetch_decodes_impl(cwslg_ctx *c, int group, uint64_t *start_epoch, cw
             const uint32_t *unused = nullptr;
             hipSetDevice(c->device);
             int rc = ft8sub_encoder(c, &unused);        // (the code first: a table without systematic form is CWSLG_ERR_ARG whatever else is there)
-            if (!rc) rc = ft8sub_module(c);
+            if (!rc) rc = group == CWSLG_GROUP_FT4 ? ft4sub_module(c) : ft8sub_module(c);
             if (rc) return rc;
         }
         if (reports && !c->sync_shared.enc_ready)
@@ -1092,7 +1095,7 @@ static int fetch_decodes_impl(cwslg_ctx *c, int group, uint64_t *start_epoch, cw
                 a.cap = d.cap;
                 adescs.push_back(a);
                 ap_cap_max = std::max(ap_cap_max, d.cap);
-            } else if (reports && ft4) {
+            } else if (reports && ft4 && !subtract) {
                 Ft4ReportDesc r{};
                 r.cx = b.d_cx;
                 r.rec = (const Ft4Rec *)b.d_rec;
@@ -1101,12 +1104,12 @@ static int fetch_decodes_impl(cwslg_ctx *c, int group, uint64_t *start_epoch, cw
                 r.cap = d.cap;
                 rdescs4.push_back(r);
             } else if (subtract) {
-                // (the device frame is the reference's 20 s buffer; the decoder's frame, and the subtractor's, is its first 15 s)
-                if (ch.frame_len < (size_t)F8SUB_N || ((uintptr_t)ch.d_frame[ch.frame_idx] & 15u))
-                    return fail(c, CWSLG_ERR_ARG, "channel %d: the subtractor needs a 16-byte aligned frame of at least %d samples", l.first, F8SUB_N);
+                // (the device frame is the reference's 20 s buffer; the decoder's frame, and the subtractor's, is its first 15 s -- FT4: 72576 samples)
+                if (ch.frame_len < sub_n || ((uintptr_t)ch.d_frame[ch.frame_idx] & 15u))
+                    return fail(c, CWSLG_ERR_ARG, "channel %d: the subtractor needs a 16-byte aligned frame of at least %d samples", l.first, (int)sub_n);
                 SubDesc r{};
                 r.frame = ch.d_frame[ch.frame_idx];
-                r.n_valid = (int)std::min(ch.frame_valid, (size_t)F8SUB_N);
+                r.n_valid = (int)std::min(ch.frame_valid, sub_n);
                 sdescs.push_back(r);               // (.resid: below, once the block is there)
                 sub_chans.push_back(l.first);
             } else if (reports) {
@@ -1135,17 +1138,17 @@ static int fetch_decodes_impl(cwslg_ctx *c, int group, uint64_t *start_epoch, cw
         if (subtract) {
             // the group's residual block, a frame per channel that takes part.  Only calls that hs.mu serialises and that synchronise before they
             // return write it, and the residual fetches take hs.mu: none is in flight now.  Its epoch is withdrawn until this call has succeeded
-            Ft8SubStage &st = c->ft8sub;
+            Ft8SubStage &st = sub_stage;
             st.resid_epoch = 0;
             st.resid_chans.clear();
-            const size_t need = sdescs.size() * (size_t)F8SUB_N * sizeof(float);
+            const size_t need = sdescs.size() * sub_n * sizeof(float);
             if (st.resid_bytes < need) {
                 if (st.d_resid) (void)hipFree(st.d_resid);
                 st.d_resid = nullptr; st.resid_bytes = 0;
                 HIPCHK(c, hipMalloc((void **)&st.d_resid, need));
                 st.resid_bytes = need;
             }
-            for (size_t i = 0; i < sdescs.size(); ++i) sdescs[i].resid = st.d_resid + i * (size_t)F8SUB_N;
+            for (size_t i = 0; i < sdescs.size(); ++i) sdescs[i].resid = st.d_resid + i * sub_n;
         }
         if (ap) {
             // the group's AP staging: per channel cap records of 20 bytes (FT4: 3 cap of 60), then their dmin words (FT4: three per record),
@@ -1215,11 +1218,11 @@ static int fetch_decodes_impl(cwslg_ctx *c, int group, uint64_t *start_epoch, cw
     if (ap) ap_launch_annotate(rf.fs, (const ApDesc *)(hs.d + adesc_at), d_offsets, d_out, (int)nch, (int)lim, ft4);
     if (subtract) {
         // what was emitted decides the size of the fit records: the head comes down first
-        Ft8SubStage &st = c->ft8sub;
+        Ft8SubStage &st = sub_stage;
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipMemcpyAsync(h_out, d_out, HARVEST_HEAD_WORDS * sizeof(unsigned), hipMemcpyDeviceToHost, rf.fs));
         HIPCHK(c, hipStreamSynchronize(rf.fs));
-        const size_t n_emit = std::min((size_t)h_out[0], lim), need = n_emit * F8SUB_REC_WORDS * sizeof(unsigned);
+        const size_t n_emit = std::min((size_t)h_out[0], lim), need = n_emit * sub_rec_words * sizeof(unsigned);
         if (st.recs_bytes < need) {
             if (st.d_recs) (void)hipFree(st.d_recs);
             st.d_recs = nullptr; st.recs_bytes = 0;
@@ -1227,7 +1230,7 @@ static int fetch_decodes_impl(cwslg_ctx *c, int group, uint64_t *start_epoch, cw
             st.recs_bytes = need + need / 2;
         }
         HIPCHK(c, ft8sub_launch(st.fit, st.apply, rf.fs, (const SubDesc *)(hs.d + pad(desc_bytes)), d_offsets, d_out, d_enc, (unsigned *)st.d_recs, d_out + rep_at,
-                                (int)nch, (int)n_emit, (int)lim));
+                                (int)nch, (int)n_emit, (int)lim, ft4 ? F4SUB_NTILE : F8SUB_NTILE));
     } else if (reports && ft4)
         ft4_report_launch(rf.fs, (const Ft4ReportDesc *)(hs.d + pad(desc_bytes)), d_offsets, d_out, d_enc, d_out + rep_at, tb4, d_w32, (int)nch, (int)lim);
     else if (reports)
@@ -1240,8 +1243,8 @@ static int fetch_decodes_impl(cwslg_ctx *c, int group, uint64_t *start_epoch, cw
     if (got && rep) std::memcpy(rep, h_out + rep_at, got * sizeof(cwslg_decode_report));
     if (got && sub) std::memcpy(sub, h_out + rep_at, got * sizeof(cwslg_subtract_report));
     if (subtract) {
-        c->ft8sub.resid_chans = sub_chans;
-        c->ft8sub.resid_epoch = *start_epoch;
+        sub_stage.resid_chans = sub_chans;
+        sub_stage.resid_epoch = *start_epoch;
     }
     *n = (int)got;
     *n_total = (int)total;
@@ -1332,13 +1335,22 @@ int cwslg_subtract_ft8(cwslg_ctx *c, uint64_t *start_epoch, cwslg_decode *dec, c
     return fetch_decodes_impl(c, CWSLG_GROUP_FT8, start_epoch, dec, nullptr, max, n, n_total, n_channels, FETCH_SUBTRACT, sub);
 }
 
-// A channel's residual: valid only while the block's epoch is the channel's frame epoch.  *slot: its place in the block.  Caller holds
-// harvest[0].mu and c->mu.
-static int residual_slot(cwslg_ctx *c, int ch_id, size_t *slot, uint64_t *start_epoch)
+// FT4 signal subtraction (the header's "FT4 signal subtraction"): the same path for the FT4 group, on lib/cwslgpu_ft4sub.hsaco's two kernels.
+int cwslg_subtract_ft4(cwslg_ctx *c, uint64_t *start_epoch, cwslg_decode *dec, cwslg_subtract_report *sub, int max, int *n, int *n_total, int *n_channels)
+{
+    if (n) *n = 0;
+    if (n_total) *n_total = 0;
+    if (n_channels) *n_channels = 0;
+    if (!c || !start_epoch || !n || !n_total) return CWSLG_ERR_ARG;
+    return fetch_decodes_impl(c, CWSLG_GROUP_FT4, start_epoch, dec, nullptr, max, n, n_total, n_channels, FETCH_SUBTRACT, sub);
+}
+
+// A channel's residual in the stage `st` (the FT8 group's or the FT4 group's): valid only while the block's epoch is the channel's frame epoch.
+// *slot: its place in the block.  A channel of the other group is in no block of this one.  Caller holds the group's harvest[].mu and c->mu.
+static int residual_slot(cwslg_ctx *c, const Ft8SubStage &st, int ch_id, size_t *slot, uint64_t *start_epoch)
 {
     if (ch_id < 0 || ch_id >= (int)c->chans.size() || !c->chans[ch_id].open) return fail(c, CWSLG_ERR_ARG, "bad channel id");
     const Channel &ch = c->chans[ch_id];
-    const Ft8SubStage &st = c->ft8sub;
     if (!ch.have_frame || !st.resid_epoch || ch.frame_t0 != st.resid_epoch) return CWSLG_ERR_NO_FRAME;
     const auto it = std::find(st.resid_chans.begin(), st.resid_chans.end(), ch_id);
     if (it == st.resid_chans.end()) return CWSLG_ERR_NO_FRAME;
@@ -1347,43 +1359,64 @@ static int residual_slot(cwslg_ctx *c, int ch_id, size_t *slot, uint64_t *start_
     return CWSLG_OK;
 }
 
-int cwslg_fetch_ft8_residual(cwslg_ctx *c, int ch_id, float *dst, size_t cap, size_t *n_valid, uint64_t *start_epoch)
+// ft4: the FT4 group's stage, lock and frame length (72576); else the FT8 group's (180000)
+static int fetch_residual_impl(cwslg_ctx *c, bool ft4, int ch_id, float *dst, size_t cap, size_t *n_valid, uint64_t *start_epoch)
 {
     if (n_valid) *n_valid = 0;
     if (!c || !dst) return CWSLG_ERR_ARG;
-    std::lock_guard<std::mutex> serial(c->harvest[0].mu);
+    std::lock_guard<std::mutex> serial(c->harvest[ft4 ? 1 : 0].mu);
     std::lock_guard<std::mutex> g(c->mu);
+    const Ft8SubStage &st = ft4 ? c->ft4sub : c->ft8sub;
+    const size_t sub_n = ft4 ? F4SUB_N : F8SUB_N;
     size_t slot = 0;
-    const int rc = residual_slot(c, ch_id, &slot, start_epoch);
+    const int rc = residual_slot(c, st, ch_id, &slot, start_epoch);
     if (rc) return rc;
-    if (cap < (size_t)F8SUB_N) return fail(c, CWSLG_ERR_ARG, "destination holds %zu samples, a residual has %d", cap, F8SUB_N);
+    if (cap < sub_n) return fail(c, CWSLG_ERR_ARG, "destination holds %zu samples, a residual has %d", cap, (int)sub_n);
     hipSetDevice(c->device);
     // (the call that wrote the block synchronised its stream before it returned)
-    HIPCHK(c, hipMemcpyAsync(dst, c->ft8sub.d_resid + slot * (size_t)F8SUB_N, (size_t)F8SUB_N * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dst, st.d_resid + slot * sub_n, sub_n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (n_valid) *n_valid = (size_t)F8SUB_N;
+    if (n_valid) *n_valid = sub_n;
     return CWSLG_OK;
 }
 
-int cwslg_ft8_residual_device_ptr(cwslg_ctx *c, int ch_id, const float **d_f32, uint64_t *start_epoch)
+static int residual_device_ptr_impl(cwslg_ctx *c, bool ft4, int ch_id, const float **d_f32, uint64_t *start_epoch)
 {
     if (d_f32) *d_f32 = nullptr;
     if (!c || !d_f32) return CWSLG_ERR_ARG;
-    std::lock_guard<std::mutex> serial(c->harvest[0].mu);
+    std::lock_guard<std::mutex> serial(c->harvest[ft4 ? 1 : 0].mu);
     std::lock_guard<std::mutex> g(c->mu);
+    const Ft8SubStage &st = ft4 ? c->ft4sub : c->ft8sub;
     size_t slot = 0;
-    const int rc = residual_slot(c, ch_id, &slot, start_epoch);
+    const int rc = residual_slot(c, st, ch_id, &slot, start_epoch);
     if (rc) return rc;
-    *d_f32 = c->ft8sub.d_resid + slot * (size_t)F8SUB_N;
+    *d_f32 = st.d_resid + slot * (size_t)(ft4 ? F4SUB_N : F8SUB_N);
     return CWSLG_OK;
 }
 
+int cwslg_fetch_ft8_residual(cwslg_ctx *c, int ch_id, float *dst, size_t cap, size_t *n_valid, uint64_t *start_epoch)
+{
+    return fetch_residual_impl(c, false, ch_id, dst, cap, n_valid, start_epoch);
+}
+int cwslg_ft8_residual_device_ptr(cwslg_ctx *c, int ch_id, const float **d_f32, uint64_t *start_epoch) { return residual_device_ptr_impl(c, false, ch_id, d_f32, start_epoch); }
+int cwslg_fetch_ft4_residual(cwslg_ctx *c, int ch_id, float *dst, size_t cap, size_t *n_valid, uint64_t *start_epoch)
+{
+    return fetch_residual_impl(c, true, ch_id, dst, cap, n_valid, start_epoch);
+}
+int cwslg_ft4_residual_device_ptr(cwslg_ctx *c, int ch_id, const float **d_f32, uint64_t *start_epoch) { return residual_device_ptr_impl(c, true, ch_id, d_f32, start_epoch); }
+
 // The same two kernels on caller-supplied frames and items: temporary device buffers, the context's stream, synchronous (cwslg_ldpc_decode's
 // pattern).  The items are laid out as the harvest lays out its records (head, 10 dwords each, per-frame offsets), which is what the kernels read.
-int cwslg_ft8_subtract_flat(cwslg_ctx *c, const float *audio, int n_frames, const cwslg_ft8_sub_item *items, int n_items, cwslg_subtract_report *sub,
-                            float *residual)
+// cwslg_ft8_sub_item and cwslg_ft4_sub_item have one layout; ft4 chooses the module, the frame length and the fit record.
+static_assert(sizeof(cwslg_ft4_sub_item) == sizeof(cwslg_ft8_sub_item) && offsetof(cwslg_ft4_sub_item, bits) == offsetof(cwslg_ft8_sub_item, bits)
+              && offsetof(cwslg_ft4_sub_item, freq_hz) == offsetof(cwslg_ft8_sub_item, freq_hz) && offsetof(cwslg_ft4_sub_item, dt_s) == offsetof(cwslg_ft8_sub_item, dt_s),
+              "one item layout");
+static_assert(CWSLG_FT4_FRAME_SAMPLES == F4SUB_N && CWSLG_FT8_FRAME_SAMPLES == F8SUB_N, "the header's frame lengths");
+static int subtract_flat_impl(cwslg_ctx *c, bool ft4, const float *audio, int n_frames, const cwslg_ft8_sub_item *items, int n_items, cwslg_subtract_report *sub,
+                              float *residual)
 {
     if (!c || n_frames < 1 || n_items < 0 || !audio || (n_items > 0 && (!items || !sub))) return CWSLG_ERR_ARG;
+    const size_t sub_n = ft4 ? F4SUB_N : F8SUB_N, sub_rec_words = ft4 ? F4SUB_REC_WORDS : F8SUB_REC_WORDS;
     std::lock_guard<std::mutex> report_serial(c->report_mu);       // (the encoder's device copy, as the report calls)
     std::lock_guard<std::mutex> g(c->mu);
     std::vector<unsigned> offsets((size_t)n_frames, 0u), out((size_t)HARVEST_HEAD_WORDS + (size_t)n_items * HARVEST_REC_WORDS, 0u);
@@ -1405,35 +1438,48 @@ int cwslg_ft8_subtract_flat(cwslg_ctx *c, const float *audio, int n_frames, cons
     hipSetDevice(c->device);
     const uint32_t *d_enc = nullptr;
     int rc = ft8sub_encoder(c, &d_enc);
-    if (!rc) rc = ft8sub_module(c);
+    if (!rc) rc = ft4 ? ft4sub_module(c) : ft8sub_module(c);
     if (rc) return rc;
+    const Ft8SubStage &st = ft4 ? c->ft4sub : c->ft8sub;
     auto pad = [](size_t v) { return (v + 255) & ~size_t(255); };
-    const size_t frame_bytes = (size_t)n_frames * F8SUB_N * sizeof(float);
+    const size_t frame_bytes = (size_t)n_frames * sub_n * sizeof(float);
     const size_t desc_at = 2 * pad(frame_bytes), off_at = desc_at + pad((size_t)n_frames * sizeof(SubDesc)), out_at = off_at + pad(offsets.size() * sizeof(unsigned));
     const size_t rep_at = out_at + pad(out.size() * sizeof(unsigned)), recs_at = rep_at + pad((size_t)n_items * F8SUB_REP_WORDS * sizeof(unsigned));
-    const size_t total = recs_at + (size_t)n_items * F8SUB_REC_WORDS * sizeof(unsigned);
+    const size_t total = recs_at + (size_t)n_items * sub_rec_words * sizeof(unsigned);
     char *d = nullptr;
     HIPCHK(c, hipMalloc((void **)&d, total));
     std::vector<SubDesc> descs((size_t)n_frames);
     for (int f = 0; f < n_frames; ++f) {
-        descs[f].frame = (const float *)d + (size_t)f * F8SUB_N;
-        descs[f].resid = (float *)(d + pad(frame_bytes)) + (size_t)f * F8SUB_N;
-        descs[f].n_valid = F8SUB_N;
+        descs[f].frame = (const float *)d + (size_t)f * sub_n;
+        descs[f].resid = (float *)(d + pad(frame_bytes)) + (size_t)f * sub_n;
+        descs[f].n_valid = (int)sub_n;
     }
     hipError_t e = hipMemcpyAsync(d, audio, frame_bytes, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d + desc_at, descs.data(), descs.size() * sizeof(SubDesc), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d + off_at, offsets.data(), offsets.size() * sizeof(unsigned), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d + out_at, out.data(), out.size() * sizeof(unsigned), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess)
-        e = ft8sub_launch(c->ft8sub.fit, c->ft8sub.apply, c->stream, (const SubDesc *)(d + desc_at), (const unsigned *)(d + off_at), (const unsigned *)(d + out_at), d_enc,
-                          (unsigned *)(d + recs_at), (unsigned *)(d + rep_at), n_frames, n_items, n_items);
+        e = ft8sub_launch(st.fit, st.apply, c->stream, (const SubDesc *)(d + desc_at), (const unsigned *)(d + off_at), (const unsigned *)(d + out_at), d_enc,
+                          (unsigned *)(d + recs_at), (unsigned *)(d + rep_at), n_frames, n_items, n_items, ft4 ? F4SUB_NTILE : F8SUB_NTILE);
     if (e == hipSuccess && n_items > 0) e = hipMemcpyAsync(sub, d + rep_at, (size_t)n_items * sizeof(cwslg_subtract_report), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess && residual) e = hipMemcpyAsync(residual, d + pad(frame_bytes), frame_bytes, hipMemcpyDeviceToHost, c->stream);
     const hipError_t es = hipStreamSynchronize(c->stream);       // (the host vectors above live until here)
     (void)hipFree(d);
     if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return fail(c, CWSLG_ERR_HIP, "cwslg_ft8_subtract_flat failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(c, CWSLG_ERR_HIP, "%s failed: %s", ft4 ? "cwslg_ft4_subtract_flat" : "cwslg_ft8_subtract_flat", hipGetErrorString(e));
     return CWSLG_OK;
+}
+
+int cwslg_ft8_subtract_flat(cwslg_ctx *c, const float *audio, int n_frames, const cwslg_ft8_sub_item *items, int n_items, cwslg_subtract_report *sub,
+                            float *residual)
+{
+    return subtract_flat_impl(c, false, audio, n_frames, items, n_items, sub, residual);
+}
+
+int cwslg_ft4_subtract_flat(cwslg_ctx *c, const float *audio, int n_frames, const cwslg_ft4_sub_item *items, int n_items, cwslg_subtract_report *sub,
+                            float *residual)
+{
+    return subtract_flat_impl(c, true, audio, n_frames, reinterpret_cast<const cwslg_ft8_sub_item *>(items), n_items, sub, residual);
 }
 
 int cwslg_sync_debug_fetch(cwslg_ctx *c, int ch_id, int what, void *dst, size_t cap_bytes, size_t *n_items, int *row_len)

@@ -741,8 +741,8 @@ int cwslg_ft8_tones(cwslg_ctx *ctx, const uint8_t *bits /* [12] */, uint8_t *ton
  * min(n_total, max) emitted records, ONE copy brings head, decodes and reports down, one synchronise.  Staging and the encoder's device copy are
  * as for the FT8 call; the code IN FORCE AT THE CALL is used.  A channel takes part only if its decode records are of the frame's epoch, which
  * implies that the last boundary ran the coherent stage on it: the spectrum read is that frame's.
- * Out of scope: unpacking to text, rvec, a-priori passes, a baseline-referred SNR, FT4 signal subtraction and any second pass over a residual
- * (FT8 has the subtraction, cwslg_subtract_ft8; the second pass stays out there too). */
+ * Out of scope: unpacking to text, rvec, a baseline-referred SNR, any second pass over a residual (a-priori passes and the subtraction are
+ * fetches of their own: cwslg_fetch_ft4_ap, cwslg_subtract_ft4 below; the second pass stays out there too). */
 int cwslg_fetch_ft4_decode_reports(cwslg_ctx *ctx, uint64_t *start_epoch /* in/out */, cwslg_decode *dec, cwslg_decode_report *rep, int max,
                                    int *n, int *n_total, int *n_channels);
 int cwslg_ft4_tones(cwslg_ctx *ctx, const uint8_t *bits /* [12] */, uint8_t *tones /* [103] */);
@@ -879,7 +879,7 @@ int cwslg_fetch_ft4_ap(cwslg_ctx *ctx, uint64_t *start_epoch /* in/out */, cwslg
  *    workgroup per channel and 1024-sample tile), one copy down, one synchronise.  The kernels are in a code object of their own beside the
  *    library (cwslgpu_ft8sub.hsaco), loaded by the first call; a missing file is CWSLG_ERR_ARG with a text that names it.
  *    The call has no group argument: it is the FT8 group's.  FT4 channels never take part, and a context with FT4 channels alone answers
- *    CWSLG_ERR_NO_FRAME like any call no channel takes part in; there is no FT4 subtraction to refuse with CWSLG_ERR_ARG.
+ *    CWSLG_ERR_NO_FRAME like any call no channel takes part in; the FT4 group has a call of its own, cwslg_subtract_ft4 below.
  *    The call holds the group's ticket for as long as it runs -- about 10 ms for 800 decodes against 0.2 ms for the report call -- and the
  *    group's next boundary waits for the ticket with the context locked: a boundary that arrives during the call delays every push on the
  *    context by the rest of it.  Call it right after the boundary, not just before the next one.
@@ -890,17 +890,17 @@ int cwslg_fetch_ft4_ap(cwslg_ctx *ctx, uint64_t *start_epoch /* in/out */, cwslg
  * 3. cwslg_ft8_subtract_flat runs the same two kernels on caller-supplied frames (n_frames x 180000 floats) and items, the cwslg_ldpc_decode
  *    pattern (synchronous, temporary device buffers, the context's stream): items in ascending frame order (else CWSLG_ERR_ARG), freq_hz in
  *    0..6000 and |dt_s| <= 30, dt_s in the candidate's convention (a transmission that starts at T has dt_s = T + 0.04); sub[i] reports items[i]; residual, [n_frames][180000], may be null.  n_items = 0 gives residual = audio.
- * Out of scope: a second search or decode pass over the residual, FT4, an int16 or prepareAudio-scaled residual, joint refitting of overlapping
- * signals, unpacking to text. */
+ * Out of scope: a second search or decode pass over the residual, an int16 or prepareAudio-scaled residual, joint refitting of overlapping
+ * signals, unpacking to text.  (FT4: the section below.) */
 typedef struct {
     float   f_hz;        /* refined frequency of tone 0: inc * 12000 / 2^32 in double, rounded to float */
     float   dt_s;        /* refined start: (float)(start - 6000) / 12000.0f */
     float   p_removed;   /* energy of the fitted waveform, in squared units of cwslg_fetch_audio_f32 */
     float   p_before;    /* the frame's energy in the signal's time-frequency footprint */
     float   p_after;     /* the same with this decode's fit taken out */
-    int32_t n_inside;    /* samples of the 79 x 1920 inside the frame */
-    int16_t df_steps;    /* k + k2 of the two frequency searches, each -52..52 */
-    int16_t dt_steps;    /* j - 30 of the time grid, -30..30 */
+    int32_t n_inside;    /* samples of the 79 x 1920 (FT4: 103 x 576) inside the frame */
+    int16_t df_steps;    /* k + k2 of the two frequency searches, each -52..52 (FT4: -26..26) */
+    int16_t dt_steps;    /* j - 30 of the time grid, -30..30 (FT4: j - 27, -27..27) */
 } cwslg_subtract_report;   /* 28 bytes */
 typedef struct { int32_t frame; uint8_t bits[12]; float freq_hz; float dt_s; } cwslg_ft8_sub_item;   /* 24 bytes; bits as cwslg_ft8_msg.bits */
 #define CWSLG_FT8_FRAME_SAMPLES 180000
@@ -910,6 +910,87 @@ int cwslg_fetch_ft8_residual(cwslg_ctx *ctx, int ch_id, float *dst, size_t cap, 
 int cwslg_ft8_residual_device_ptr(cwslg_ctx *ctx, int ch_id, const float **d_f32, uint64_t *start_epoch);
 int cwslg_ft8_subtract_flat(cwslg_ctx *ctx, const float *audio /* [n_frames][180000] */, int n_frames, const cwslg_ft8_sub_item *items, int n_items,
                             cwslg_subtract_report *sub, float *residual /* [n_frames][180000] or null */);
+/* FT4 signal subtraction (PARITY UNPINNED like the rest of the chain): the FT8 block above on the FT4 chain -- per decode of
+ * cwslg_fetch_decodes(CWSLG_GROUP_FT4) a refined frequency and start, fitted with the KNOWN word as the sync pattern (103 known symbols instead of
+ * 16 Costas symbols), and per channel a RESIDUAL frame: the float frame minus the fitted waveform of every emitted decode.  FT4 signals are four
+ * times as wide as FT8's and the mode is the busier one, so a weak signal under a strong one is the common case; without this call a consumer
+ * pulls 290 KB per channel to the host and synthesises and fits there.  A FETCH, not a stage: no record kind, no stamp, no launch at a boundary,
+ * no field in cwslg_stats, stats.sync_launches untouched; it never writes the frame, a plane, a list or a record.  tests/ft4_subtract_ref.py
+ * restates everything below in numpy, bit for bit.  Every float operation is one un-fused float32 operation in the order written; phases are
+ * uint32 arithmetic modulo 2^32, in units of 2^-32 turns.
+ *   Frame: the decoder's -- the first 72576 samples (CWSLG_FT4_FRAME_SAMPLES) of the channel's float frame; samples at or past the frame's
+ *       n_valid count as +0.
+ *   Tables (cwsl_digi_amd/csrc/modules/ft4sub_tables.inc, written by scripts/gen_ft4sub_tables.py): CP[3][576], CPT[3], COSQ[1025], WIN[97];
+ *       COSQ and WIN are the FT8 tables value for value (both modes have 32 blocks per symbol).
+ *   Waveform of (tones t[0..102] -- what cwslg_ft4_tones returns: the reports' re-encoding through the FT4 mapping, no rvec --, increment inc):
+ *       GFSK, BT = 1.0, tone unit 12000 / 576 Hz, unit amplitude, 103 x 576 samples at 12 kHz.  Sample v of symbol n has phase
+ *       base[n] + v inc + tp CP[2][v] + tc CP[1][v] + tn CP[0][v],  tp / tc / tn the tones of symbols n - 1 / n / n + 1 (clamped to 0..102: the
+ *       first and last tone are held outside the transmission; the protocol's two ramp symbols are NOT modelled, the amplitude track absorbs
+ *       them); base[0] = 0, base[n + 1] = base[n] + 576 inc + tp CPT[2] + tc CPT[1] + tn CPT[0].  (cos, sin) = CS[(phase + 2^19) >> 20] from
+ *       the quarter-turn table by symmetry, exactly as for FT8.  No sinf / cosf anywhere.
+ *   Start: i0 = (int)clamp(rintf((dt_s + 0.5f) * 12000.0f), -400000, 400000) - F4SUB_CAND_OFFSET; inc0 = (uint32)llrint((double)f1_hz * 2^32 /
+ *       12000).  F4SUB_CAND_OFFSET = 0: a record's dt_s is ibest / 666.67 - 0.5 with ibest the baseband sample (18 frame samples) at which the
+ *       first Costas symbol starts, so it names the transmission's first sample itself, to within half a baseband sample.  Established on the
+ *       CPU with the float64 synthesiser (tests/ft4_gfsk.py) against the oracle's FT4 search and refinement: over starts on and off the 666.67 Hz
+ *       grid the record's dt_s lay -6.1 .. +3.6 samples from the truth, never a whole step to one side.  FT8's 480 has no twin.
+ *   Block sums of a start s and an increment: the signal's 59328 samples in 3296 blocks of 18 (32 per symbol, block rate 666.67 Hz); B[b] = (re,
+ *       im), re = re + x c and im = im - x s over the block's samples in ascending order from +0; a sample outside 0..72575 is +0.
+ *   Symbol metric: S[n] = the symbol's 32 block sums halved (a[l] = a[l] + a[l + h] for l < h, h = 16, 8, 4, 2, 1), per component; M = sum over
+ *       n = 0..102 ascending, from +0, of (S.re S.re + S.im S.im).
+ *   FIT, from the ORIGINAL frame for every decode:
+ *     1. frequency, at block rate: B at (i0, inc0); for k = -26..26: B'[b] = (re cr + im sr, im cr - re sr), (cr, sr) = CS of the phase
+ *        (uint32)(k 27962) * (18 b + 9); the FIRST maximum of M over ascending k wins; inc = inc0 + k 27962.  The grid is 0.078124 Hz wide
+ *        (27962 * 12000 / 2^32: 0.4 / T for the 4.94 s signal, as FT8's) and reaches +-2.03 Hz: f1_hz sits on the refinement's 1 Hz grid around
+ *        a peak-interpolated f0_hz.
+ *     2. time, at sample rate and at the refined frequency: for j = 0..54: M of the block sums at (i0 - 54 + 2 j, inc); the FIRST maximum over
+ *        ascending j wins; start = i0 - 54 + 2 j.  The step is 2 samples (2/576 of a symbol against FT8's 8/1920); +-54 samples is three
+ *        samples of the 666.67 Hz baseband in which ibest was found.
+ *     3. frequency once more: step 1 on B at (start, inc), inc = inc + k2 27962 (df_steps = k + k2).  B at (start, inc); cnt[b] = samples of
+ *        block b inside 0..72575.
+ *     4. amplitude track: the FT8 rule with WIN[97] over blocks b - 48 .. b + 48 (three symbols), blocks outside 0..3295 contributing +0,
+ *        normalised by the samples under the window; den > 0 else a[b] = +0.
+ *     4a. the track's phase slope, a step FT8 does not have.  The symbol metric of steps 1 and 3 is not coherent across symbols, and over FT4's
+ *        48 ms symbol it falls by only 4.6e-5 of its value per grid step: a neighbour one tone spacing away moves its maximum by a step (measured:
+ *        0.09 Hz).  What the searches leave of the frequency turns the track from block to block, coherently over the whole
+ *        signal: num = sum of (a[b+1].im a[b].re - a[b+1].re a[b].im), den = sum of (a[b+1].re a[b].re + a[b+1].im a[b].im) over b = 0..3294
+ *        (two products and one sum or difference each; block 3295 contributes +0; summed as the figures of step 5 are); den > 0: d =
+ *        (double)(num / den) * (2^32 / (6.283185307179586 * 18)) -- the small-angle tangent, radians per block to 2^-32 turns per sample --
+ *        clamped to +-2 * 27962 (the searches are trusted to two grid steps; a NaN takes the lower bound), inc = inc + (int)rint(d); otherwise
+ *        inc stays.  Then B at (start, inc) and step 4 once more: the track the record and the figures hold is the second one.  df_steps still
+ *        counts the two searches alone.
+ *     5. figures p_removed, p_before, p_after: the FT8 terms, summed as thread l of 256 adds the terms of blocks l, l + 256, .. ascending from
+ *        +0 (13 rows), then a[l] = a[l] + a[l + h] for l < h, h = 128 .. 1.  The footprint is 666.67 Hz wide around the tone.
+ *   APPLY: r = r - 2.0f * y one decode after the other IN EMISSION ORDER in a register, no atomics; y = ar c - ai s at signal sample u = t - start
+ *       (0 <= u < 59328, t inside the frame), (ar, ai) the track between block centres (sample 18 b + 8.5): pp = 2 u - 17; pp < 0: a[0];
+ *       b0 = min(pp / 36, 3294), m = pp - 36 b0; m >= 36: a[3295]; otherwise a[b0] + ((float)m * (1.0f / 36.0f)) * (a[b0 + 1] - a[b0]).
+ * 1. cwslg_subtract_ft4 is cwslg_fetch_ft4_decode_reports' contract for the FT4 group with sub[p] the cwslg_subtract_report of dec[p] (the same
+ *    28-byte struct; df_steps is k + k2, each -26..26, dt_steps is j - 27, -27..27; n_inside counts the 103 x 576 samples inside the frame;
+ *    dt_s is (float)(start - 6000) / 12000.0f).  Everything point 1 of the FT8 section says holds: one ticket, one serialised call, the fetch
+ *    stream, a systematic code or CWSLG_ERR_ARG, dec byte-identical to cwslg_fetch_decodes(CWSLG_GROUP_FT4) for that epoch and max, either
+ *    output pointer nullable.  The residual block belongs to the FT4 group: allocated by the first call, grown on demand, freed by
+ *    cwslg_destroy; a channel without an emitted decode -- and every channel at max = 0 -- gets the frame's own bits.  Two calls on one epoch
+ *    leave the same bytes.  FT8 channels never take part; a context with FT8 channels alone answers CWSLG_ERR_NO_FRAME.  A frame shorter than
+ *    72576 samples or not 16-byte aligned is CWSLG_ERR_ARG.  Execution: descriptors up, the three harvest launches, the 16-byte head down and
+ *    one synchronise (the fit records, 26896 bytes each, are sized by what was emitted), ft4_sub_fit_kernel (one workgroup per emitted decode),
+ *    ft4_sub_apply_kernel (one workgroup per channel and 1024-sample tile, 71 tiles), one copy down, one synchronise.  f_hz is the final
+ *    inc (step 4a included) * 12000 / 2^32.  The kernels are in a
+ *    third code object beside the library (cwslgpu_ft4sub.hsaco), loaded by the first call; a missing file is CWSLG_ERR_ARG
+ *    with a text that names it.  The call holds the group's ticket while it runs: call it right after the boundary.
+ * 2. cwslg_fetch_ft4_residual copies a channel's residual (72576 floats; cap below that: CWSLG_ERR_ARG) and cwslg_ft4_residual_device_ptr hands
+ *    out its device address; both only while the block's epoch is the channel's frame epoch, otherwise CWSLG_ERR_NO_FRAME.  An FT8 channel's id
+ *    answers CWSLG_ERR_NO_FRAME.  An address handed out is dead from the next cwslg_subtract_ft4 call on.
+ * 3. cwslg_ft4_subtract_flat runs the same two kernels on caller-supplied frames (n_frames x 72576 floats) and items, under the argument rules of
+ *    cwslg_ft8_subtract_flat; dt_s in the record's convention (a transmission that starts at T seconds into the frame has dt_s = T - 0.5).
+ * Out of scope: a second search or decode pass over the residual, an int16 or prepareAudio-scaled residual, rvec, joint refitting of overlapping
+ * signals, unpacking to text. */
+typedef struct { int32_t frame; uint8_t bits[12]; float freq_hz; float dt_s; } cwslg_ft4_sub_item;   /* 24 bytes; cwslg_ft8_sub_item's layout; freq_hz: the record's f1_hz */
+#define CWSLG_FT4_FRAME_SAMPLES 72576
+int cwslg_subtract_ft4(cwslg_ctx *ctx, uint64_t *start_epoch /* in/out */, cwslg_decode *dec, cwslg_subtract_report *sub, int max, int *n, int *n_total,
+                       int *n_channels);
+int cwslg_fetch_ft4_residual(cwslg_ctx *ctx, int ch_id, float *dst, size_t cap, size_t *n_valid, uint64_t *start_epoch);
+int cwslg_ft4_residual_device_ptr(cwslg_ctx *ctx, int ch_id, const float **d_f32, uint64_t *start_epoch);
+int cwslg_ft4_subtract_flat(cwslg_ctx *ctx, const float *audio /* [n_frames][72576] */, int n_frames, const cwslg_ft4_sub_item *items, int n_items,
+                            cwslg_subtract_report *sub, float *residual /* [n_frames][72576] or null */);
 int cwslg_fetch_slot(cwslg_ctx *ctx, int ch_id, int16_t *frame, size_t cap, void *list, size_t list_bytes,
                      cwslg_ft4_sync *ft4, int max_ft4, cwslg_slot_result *out);
 int cwslg_set_ft4_syncmin(cwslg_ctx *ctx, float syncmin);

@@ -209,6 +209,43 @@ public:
         check(c_, cwslg_ft8_subtract_flat(c_, audio, nFrames, items.empty() ? nullptr : items.data(), static_cast<int>(items.size()),
                                           sub.empty() ? nullptr : sub.data(), residual ? residual->data() : nullptr));
     }
+    // FT4 signal subtraction (cwslg_subtract_ft4): the same for the FT4 group -- fetchDecodes("FT4") with a refined fit per decode and a residual
+    // of 72576 floats per FT4 channel (ft4Residual, ft4ResidualDevice; false for an FT8 channel's id).  ft4SubtractFlat: frames of 72576 floats.
+    int subtractFt4(std::vector<cwslg_decode> &out, std::vector<cwslg_subtract_report> &sub, std::uint64_t &startEpoch, int max = 4096, int *nChannels = nullptr)
+    {
+        out.resize(max > 0 ? max : 0);
+        sub.resize(out.size());
+        int n = 0, total = 0;
+        const int rc = cwslg_subtract_ft4(c_, &startEpoch, out.data(), sub.data(), static_cast<int>(out.size()), &n, &total, nChannels);
+        if (rc == CWSLG_ERR_NO_FRAME) { out.clear(); sub.clear(); return 0; }
+        check(c_, rc);
+        out.resize(n);
+        sub.resize(n);
+        return total;
+    }
+    bool ft4Residual(int chId, std::vector<float> &out, std::uint64_t *startEpoch = nullptr)
+    {
+        out.resize(CWSLG_FT4_FRAME_SAMPLES);
+        const int rc = cwslg_fetch_ft4_residual(c_, chId, out.data(), out.size(), nullptr, startEpoch);
+        if (rc == CWSLG_ERR_NO_FRAME) { out.clear(); return false; }
+        check(c_, rc);
+        return true;
+    }
+    bool ft4ResidualDevice(int chId, const float *&dF32, std::uint64_t *startEpoch = nullptr)
+    {
+        const int rc = cwslg_ft4_residual_device_ptr(c_, chId, &dF32, startEpoch);
+        if (rc == CWSLG_ERR_NO_FRAME) return false;
+        check(c_, rc);
+        return true;
+    }
+    void ft4SubtractFlat(const float *audio, int nFrames, const std::vector<cwslg_ft4_sub_item> &items, std::vector<cwslg_subtract_report> &sub,
+                         std::vector<float> *residual = nullptr)
+    {
+        sub.resize(items.size());
+        if (residual) residual->resize(static_cast<std::size_t>(nFrames > 0 ? nFrames : 0) * CWSLG_FT4_FRAME_SAMPLES);
+        check(c_, cwslg_ft4_subtract_flat(c_, audio, nFrames, items.empty() ? nullptr : items.data(), static_cast<int>(items.size()),
+                                          sub.empty() ? nullptr : sub.data(), residual ? residual->data() : nullptr));
+    }
     // FT8 a-priori decoding: the patterns are the caller's data (cwslg_set_ft8_ap validates them: at most 8, none clears them), tried in this
     // order on the candidates BP and OSD gave up on.  apDecode runs the kernel on caller-supplied metrics; fetchFt8Ap is fetchDecodes' shape for
     // the a-priori words of the FT8 group (by_osd = 2, set = the pattern, dmin = OSD's distance of the word): words BP / OSD already have are
