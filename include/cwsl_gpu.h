@@ -890,6 +890,8 @@ int cwslg_fetch_ft4_ap(cwslg_ctx *ctx, uint64_t *start_epoch /* in/out */, cwslg
  * 3. cwslg_ft8_subtract_flat runs the same two kernels on caller-supplied frames (n_frames x 180000 floats) and items, the cwslg_ldpc_decode
  *    pattern (synchronous, temporary device buffers, the context's stream): items in ascending frame order (else CWSLG_ERR_ARG), freq_hz in
  *    0..6000 and |dt_s| <= 30, dt_s in the candidate's convention (a transmission that starts at T has dt_s = T + 0.04); sub[i] reports items[i]; residual, [n_frames][180000], may be null.  n_items = 0 gives residual = audio.
+ *    The increment is uint32 throughout: where the searches step it below 0 (freq_hz = 0 and k + k2 < 0) it wraps, and f_hz reports the wrapped
+ *    increment by the formula above, a value just under 12000 (11999.75 at k + k2 = -8), not a negative frequency.
  * Out of scope: a second search or decode pass over the residual, an int16 or prepareAudio-scaled residual, joint refitting of overlapping
  * signals, unpacking to text.  (FT4: the section below.) */
 typedef struct {
@@ -973,7 +975,8 @@ int cwslg_ft8_subtract_flat(cwslg_ctx *ctx, const float *audio /* [n_frames][180
  *    72576 samples or not 16-byte aligned is CWSLG_ERR_ARG.  Execution: descriptors up, the three harvest launches, the 16-byte head down and
  *    one synchronise (the fit records, 26896 bytes each, are sized by what was emitted), ft4_sub_fit_kernel (one workgroup per emitted decode),
  *    ft4_sub_apply_kernel (one workgroup per channel and 1024-sample tile, 71 tiles), one copy down, one synchronise.  f_hz is the final
- *    inc (step 4a included) * 12000 / 2^32.  The kernels are in a
+ *    inc (step 4a included) * 12000 / 2^32; an increment that the searches or step 4a took below 0 (freq_hz = 0 in the flat call) has wrapped
+ *    modulo 2^32 and is reported as it stands, a value just under 12000, as for FT8.  The kernels are in a
  *    third code object beside the library (cwslgpu_ft4sub.hsaco), loaded by the first call; a missing file is CWSLG_ERR_ARG
  *    with a text that names it.  The call holds the group's ticket while it runs: call it right after the boundary.
  * 2. cwslg_fetch_ft4_residual copies a channel's residual (72576 floats; cap below that: CWSLG_ERR_ARG) and cwslg_ft4_residual_device_ptr hands

@@ -1,6 +1,10 @@
 """GPU: the FT8 subtractor's two kernels through cwslg_ft8_subtract_flat (include/cwsl_gpu.h, "FT8 signal subtraction"; modules/ft8sub.hip), byte for
 byte against the numpy restatement (tests/ft8_subtract_ref.py) on tests/ft8_subtract_cases.py's frames; the roster of the module's code object
- and its freedom from scratch memory."""
+ and its freedom from scratch memory.
+tests/ft8_subtract_edge_cases.py adds the inputs whose window starts have every remainder w0 mod 4, items at the limits of dt_s and freq_hz, and a
+table of offsets with runs of equal entries (tests/test_subtract_edge_inputs.py: what each contains, on the CPU).
+Times of the flat-call tests on one MI355X, the restatement on the host included (it is most of each): zero_one_four 0.20 s; offgrid 0.28, limits 0.27, crowded 1.04, reversed 0.94 (before its fits were shared with crowded's), trailing 0.04 s.  crowded is 27 fits of the restatement,
+about 0.04 s each there, which is what it takes to put 24 records on one walk of the apply kernel."""
 import os
 import re
 
@@ -8,6 +12,7 @@ import numpy as np
 import pytest
 
 import ft8_subtract_cases as SC
+import ft8_subtract_edge_cases as EC
 import ft8_subtract_ref as S
 import ldpc_cases as LC
 import report_kernel_cases as K
@@ -52,8 +57,8 @@ def fctx():
     c.close()
 
 
-def _compare(got_sub, got_res, name):
-    want_sub, want_res = SC.kernel_reference(name)
+def _compare(got_sub, got_res, name, cases=SC):
+    want_sub, want_res = cases.kernel_reference(name)
     assert got_sub.dtype.itemsize == S.SUB_DTYPE.itemsize and len(got_sub) == len(want_sub)
     bad = [i for i in range(len(want_sub)) if got_sub[i].tobytes() != want_sub[i].tobytes()]
     assert not bad, (bad, got_sub[bad[:3]], want_sub[bad[:3]])
@@ -80,6 +85,28 @@ def test_flat_call_against_the_restatement(fctx, name):
         assert (want_sub["p_after"][strong] < 0.2 * want_sub["p_before"][strong]).all()
     if name == "edges":
         assert (want_sub["n_inside"] < S.NW).all() and (want_sub["n_inside"] > 0).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", EC.NAMES)
+def test_flat_call_on_the_edge_cases(fctx, name):
+    """tests/ft8_subtract_edge_cases.py (what each case contains: tests/test_subtract_edge_inputs.py): window starts with every remainder
+    w0 mod 4, items at the limits of dt_s and freq_hz, 8 frames with items on three of them and 24 on one, those 24 in reverse order, and two
+    trailing frames without an item"""
+    audio, items = EC.kernel_cases()[name]
+    sub, res = fctx.ft8_subtract_flat(audio, items)
+    _compare(sub, res, name, EC)
+    if name == "limits":
+        assert np.isfinite([[float(sub[i][f]) for f in ("f_hz", "dt_s", "p_removed", "p_before", "p_after")] for i in range(len(sub))]).all()
+        assert np.isfinite(res).all()
+        for i in (0, 1):                                                # dt_s = +30, -30: wholly outside the frame
+            assert abs(float(items["dt_s"][i])) == 30.0 and sub["n_inside"][i] == 0
+            assert all(sub[f][i].tobytes() == np.float32(0).tobytes() for f in ("p_removed", "p_before", "p_after"))
+    if name == "crowded":
+        for f in (1, 2, 4, 5, 6):                                       # the frames without an item: their own bits
+            assert res[f].tobytes() == audio[f].tobytes()
+    if name == "trailing":
+        assert res[1:].tobytes() == audio[1:].tobytes()
 
 
 @pytest.mark.gpu

@@ -1,6 +1,9 @@
 """GPU: cwslg_subtract_ft8 on the chain (include/cwsl_gpu.h, "FT8 signal subtraction") -- 3 channels x 1 slot, the smallest group that has a channel
 with several decodes, one with one and one with none.  Every comparison is byte for byte: `dec` against cwslg_fetch_decodes, `sub` and every
-residual against tests/ft8_subtract_ref.py applied to the GPU's own float frame (cwslg_fetch_audio_f32) and `dec`."""
+residual against tests/ft8_subtract_ref.py applied to the GPU's own float frame (cwslg_fetch_audio_f32) and `dec`.
+On fresh contexts: a slot that ends early after two full ones (the n_valid masks against a stale tail), every `max` from 0 to beyond the total, and
+nine channels opened after a first call (the residual block made anew).  Times on one MI355X, the restatement on the host included:
+test_slot_against_the_restatement 0.17 s; the short slot 0.18, every max 0.22, the grown block 0.19 s."""
 import ctypes as C
 import functools
 
@@ -39,8 +42,11 @@ def _open(ctx, seed=SEED, code=None):
     return rx, chans
 
 
-def _slot(ctx, rx, e):
+def _slot(ctx, rx, e, n_blocks=None):
+    """n_blocks: a slot that ends early, after that many receiver blocks of IQ"""
     iq, step = OC.chain_iq(SEED), 64 * RC.BLK[MODE]                      # (every slot carries the same IQ: the epochs differ, which is what matters here)
+    if n_blocks is not None:
+        iq = iq[:n_blocks * RC.BLK[MODE]]
     for k in range(0, len(iq), step):
         ctx.push_iq(rx, iq[k:k + step])
     ctx.slot_boundary(MODE, RC.start_epoch(MODE, e + 1))
@@ -203,6 +209,113 @@ def test_fast_mode_frame():
         _slot(c, rx, 0)
         got = _check(c, chans, BIG, "fast-all")
         assert got[3] >= 1
+
+
+SHORT_BLOCKS = 302                 # receiver blocks of the slot that ends early
+
+
+def _device_floats(ctx, ptr, n):
+    """n floats at a device address, through the HIP runtime the library itself is linked to"""
+    out = np.empty(n, np.float32)
+    ctx.synchronize()
+    ctx.L.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    assert ctx.L.hipMemcpy(out.ctypes.data, ptr, 4 * n, 2) == 0         # (2: hipMemcpyDeviceToHost)
+    return out
+
+
+def test_short_slot_after_two_full_ones():
+    """A slot that ended early, after two full ones have left a loud full-length frame in both of the channel's device buffers: the device frame
+    does not hold the zero tail, so desc.n_valid is what keeps the fit's window and the apply's frame load from the earlier slot's samples.
+    The reference is the restatement on cwslg_fetch_audio_f32's frame, whose tail is +0.  n_valid lies inside the span of an emitted decode.
+    The frame grows by whole receiver blocks, 512 samples each, so n_valid can only be a multiple of 4 here: the masks are reached a
+    whole vector at a time."""
+    import cwsl_digi_amd as P
+    with P.Context(0) as c:
+        rx, chans = _open(c)
+        _slot(c, rx, 0)
+        _slot(c, rx, 1)
+        _slot(c, rx, 2, SHORT_BLOCKS)
+        dec, sub, E, n_total, n_ch = _check(c, chans, BIG, "short-all")
+        assert (E, n_ch) == (RC.start_epoch(MODE, 2), 3) and n_total >= 1
+        nv = [c.fetch_audio_f32(ch)[1] for ch in chans]
+        assert len(set(nv)) == 1 and 0 < nv[0] < S.N
+        n_valid = nv[0]
+        assert n_valid % 4 == 0 and n_valid == SHORT_BLOCKS * RC.BLK[MODE] * 12000 // RC.FS
+        # where the fits put the decodes: n_valid strictly inside the span of at least one
+        start = np.rint(sub["dt_s"].astype(np.float64) * 12000.0).astype(np.int64) + 6000
+        cut = (start < n_valid) & (n_valid < start + S.NW)
+        print("short slot: n_valid", n_valid, "n_valid % 4", n_valid % 4, "decodes per channel", [int((dec["ch_id"] == ch).sum()) for ch in chans],
+              "starts", start.tolist(), "cut by n_valid", cut.tolist())
+        assert cut.any()
+        # the device frame past n_valid is NOT zero: what the slot before the last left there
+        for ch in chans:
+            i16, f32 = c.frame_device_ptrs(ch)
+            dev = _device_floats(c, f32, S.N)
+            assert dev[:n_valid].tobytes() == c.fetch_audio_f32(ch)[0][:n_valid].tobytes()
+            assert np.count_nonzero(dev[n_valid:]) > (S.N - n_valid) // 2
+
+
+def _cut_references(ctx, chans, dec):
+    """_REF["max-<k>"] for every k = 0 .. len(dec) + 1, as _want would make them one by one: a fit reads the original frame alone, so the fits
+    are made once and the residual of a cut list is the restatement's apply over the fits that are left"""
+    G = K.encoder(SEED)
+    audio = {ch: ctx.fetch_audio_f32(ch)[0][:S.N] for ch in chans}
+    fits = [S.fit(audio[d["ch_id"]], RR.tones(G, d["bits"]), d["freq_hz"], d["dt_s"]) for d in dec]
+    sub = np.array([f[0] for f in fits], S.SUB_DTYPE).reshape(-1)
+    for k in range(len(dec) + 2):
+        _REF["max-%d" % k] = (sub[:k], {ch: S.apply(audio[ch], [f[1] for f, d in zip(fits[:k], dec[:k]) if d["ch_id"] == ch]) for ch in chans})
+
+
+def test_every_max():
+    """max = 0 .. n_total + 1: the list cut in front of the first decode, inside a channel, exactly at a channel's end (where the apply's p_lo and
+    p_hi clamp against the emitted count) and not at all"""
+    import cwsl_digi_amd as P
+    with P.Context(0) as c:
+        rx, chans = _open(c)
+        _slot(c, rx, 0)
+        n_total = c.subtract_ft8(0, BIG)[3]
+        counts = [int((c.fetch_decodes(MODE, 0, BIG)[0]["ch_id"] == ch).sum()) for ch in chans]
+        assert n_total == sum(counts) and counts[0] >= 2 and counts[1] == 1
+        _cut_references(c, chans, c.fetch_decodes(MODE, 0, BIG)[0])
+        for mx in range(n_total + 2):
+            got = _check(c, chans, mx, "max-%d" % mx)
+            assert len(got[0]) == min(mx, n_total) and got[3] == n_total
+        # (max = counts[0] ends on the first channel's boundary, counts[0] + 1 is one decode into the second)
+        assert counts[0] + 1 <= n_total
+
+
+def test_residual_block_grows_with_the_channels():
+    """The group's residual block is sized by the channels of the first call; nine more channels on the same receiver, at the first channel's
+    dial offset, take part in the next slot: the block is freed and made anew, every new channel hears what channel 0 hears and gets its reports
+    and its residual, byte for byte, and the first three still agree with the restatement."""
+    import cwsl_digi_amd as P
+    with P.Context(0) as c:
+        rx, chans = _open(c)
+        _slot(c, rx, 0)
+        assert c.subtract_ft8(0, BIG)[4] == 3
+        more = [c.channel_open(rx, RFS[0], MODE) for _ in range(9)]
+        for ch in more:
+            c.slot_boundary_channel(ch, RC.start_epoch(MODE, 1))                  # (a channel's first boundary starts its first slot)
+        _slot(c, rx, 1)
+        dec, sub, E, n_total, n_ch = c.subtract_ft8(0, BIG)
+        assert (E, n_ch) == (RC.start_epoch(MODE, 1), 12) and len(dec) == n_total
+        # the first three channels against the restatement
+        old = np.isin(dec["ch_id"], chans)
+        want_sub, want_res = _want(c, chans, dec[old], "grow-12")
+        assert sub[old].tobytes() == want_sub.tobytes()
+        for ch in chans:
+            assert c.fetch_ft8_residual(ch)[0].tobytes() == want_res[ch].tobytes()
+        # the nine new ones against channel 0
+        mine = dec["ch_id"] == chans[0]
+        assert mine.sum() >= 2
+        a0 = c.fetch_audio_f32(chans[0])[0].tobytes()
+        for ch in more:
+            assert c.fetch_audio_f32(ch)[0].tobytes() == a0
+            its = dec["ch_id"] == ch
+            assert its.sum() == mine.sum() and dec["bits"][its].tobytes() == dec["bits"][mine].tobytes()
+            assert sub[its].tobytes() == sub[mine].tobytes()
+            r, e = c.fetch_ft8_residual(ch)
+            assert e == E and r.tobytes() == want_res[chans[0]].tobytes()
 
 
 def test_residual_is_gone_after_the_next_boundary(slot):
